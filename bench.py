@@ -1,7 +1,13 @@
 """bench.py -- windows/s of the MI355X wake-word hot path (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints the headline line.
+--dump-outputs DIR writes the last timed step's logits to DIR/logits.npy (the
+clips are a pure function of --seed and the clip index, so two builds run with
+the same arguments can be compared logit for logit).  --full adds the
+torch-CPU baseline and the config 4 / 5 / 3 keys to the line (N = 1).
 
 Started without torchrun (WORLD_SIZE unset) and with --gpus N > 1, the
 process launches N ranks itself before touching the GPU: N fresh child
@@ -77,7 +83,13 @@ def parse():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=65536, help="clips per GPU per step")
     ap.add_argument("--seed", type=int, default=1234)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure what a plain run leaves out: the torch-CPU baseline and "
+                         "the config 4 / 5 / 3 keys (N=1 only; --no-cpu-baseline / --no-extras drop one of the two)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the logits of the last timed step to DIR/logits.npy "
+                         "(float32, one per clip; rank r > 0 of an N-rank run writes DIR/logits_rank<r>.npy)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the torch-CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--audio", default="f32", choices=["f32", "i16"],
                     help="sample type of the resident clips: f32 (the metric's workload, 64,000 B/window) or "
@@ -86,11 +98,14 @@ def parse():
                     help="process-group backend for the start/stop barriers and the max-over-ranks time (nccl = "
                          "RCCL over xGMI; gloo lets several ranks share one GPU for a rehearsal of the N>1 path)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the config 4 / 5 / 3 measurements added to the line after the headline (N=1 only)")
+                    help="with --full: skip the config 4 / 5 / 3 measurements added to the line after the headline")
     ap.add_argument("--precision", default="fp32", choices=list(PRECISIONS),
                     help="CNN convolutions: fp32 MFMA (config 2, default), bf16 (config 4), or bf16x3 "
                          "(config 2 at fp32-grade accuracy on split-bf16 MFMA); front-end fp32 always")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def free_port() -> int:
@@ -420,6 +435,13 @@ def main():
             dist.destroy_process_group()
         sys.exit(3)
 
+    if args.dump_outputs:
+        # what a caller of the timed path receives: the last timed step's logits
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        name = "logits.npy" if rank == 0 else f"logits_rank{rank}.npy"
+        np.save(os.path.join(args.dump_outputs, name), logits.cpu().numpy().astype(np.float32, copy=False))
+
     if rank == 0:
         total = world * B * args.steps
         value = total / elapsed
@@ -471,9 +493,9 @@ def main():
         util = load_utilisation(args.precision)
         if util:
             out["roofline"]["utilisation"] = util
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
-        if world == 1 and not shared and not args.no_extras:
+        if args.full and world == 1 and not shared and not args.no_extras:
             # SURVEY 8(d) configs 4, 5, 3, measured after the headline's timed
             # region and its CPU leg (the headline above is unchanged by them)
             # (a Python-level failure in one of them is recorded in its key; the

@@ -315,14 +315,14 @@ def test_config5_decision_parity(precision, out_scale, mix, monkeypatch):
 
 @pytest.mark.gpu
 def test_bench_line_carries_every_config(gpu):
-    """The driver's bench line (bench.py, N = 1) holds the headline and the
-    config 4 / 5 / 3 keys, each measured (no error entry)."""
+    """The driver's full bench line (bench.py --full, N = 1) holds the headline
+    and the config 4 / 5 / 3 keys, each measured (no error entry)."""
     import json
     import subprocess
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=300)
+                        "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["value"] > 0 and line["roofline"]["frac"] > 0
@@ -331,3 +331,31 @@ def test_bench_line_carries_every_config(gpu):
     assert line["config4"]["batch_per_gpu"] == 131_072 and line["config4"]["value"] > 0
     assert line["config5"]["value"] > 0 and line["config5"]["output_kernel"]["frac"] > 0
     assert line["config3"]["p50_latency_ms"] > 0
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_the_headline_alone_and_dumps_its_logits(gpu, golden_dir, tmp_path):
+    """A plain bench run (no --full) times exactly --steps steps and carries no
+    CPU baseline or config 4 / 5 / 3 key; --dump-outputs writes the timed
+    path's logits (float32, one per clip) for the clips the seed defines:
+    within the fp32 logit tolerance of Model.detect over the same clips."""
+    import json
+    import subprocess
+    import sys
+    import wakeword
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    B, seed = 1000, 77
+    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--batch", str(B), "--seed", str(seed), "--dump-outputs", str(tmp_path / "out")],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 3 and line["value"] > 0 and line["ms_per_step"] > 0
+    for key in ("cpu_baseline", "config4", "config5", "config3"):
+        assert key not in line
+    assert os.listdir(tmp_path / "out") == ["logits.npy"]
+    got = np.load(tmp_path / "out" / "logits.npy")
+    assert got.dtype == np.float32 and got.shape == (B,)
+    model = wakeword.load_onnx(os.path.join(golden_dir, "xiaoa.onnx"))
+    want = model.detect(wakeword.synth_clips(seed, 0, B, device=0)).reshape(-1).cpu().numpy()
+    assert np.abs(got - want).max() <= LOGIT_ATOL

@@ -4,7 +4,7 @@
 # writes into gpurun_out/prof_<tag>/ (gpurun merges only gpurun_out/ back); then,
 # in the build container, `bash tools/profile_round.sh <tag> --collect` copies
 # the summaries into profiles/:
-#   <tag>_bench.json          bench.py line (default config, with cpu_baseline)
+#   <tag>_bench.json          bench.py --full line (default config, with cpu_baseline and configs 4 / 5 / 3)
 #   <tag>_kernel_stats.csv    rocprofv3 --kernel-trace --stats of the same bench command
 #   <tag>_bench_profiled.json the bench line printed under rocprofv3
 #   <tag>_pmc.json            per-kernel PMC means (tools/pmc_summary.py)
@@ -27,7 +27,7 @@ shift
 BARGS="$*"
 mkdir -p "$OUT"
 cd "$R"
-timeout -k 10 300 python3 bench.py $BARGS > "$OUT/bench.log" 2> "$OUT/bench.err"
+timeout -k 10 300 python3 bench.py --full $BARGS > "$OUT/bench.log" 2> "$OUT/bench.err"
 echo "bench: $(tail -1 $OUT/bench.log | cut -c1-200)"
 cd /tmp && export TMPDIR=/tmp
 # 40 timed steps so the 2 warm-up launches weigh little in the kernel's mean; the
