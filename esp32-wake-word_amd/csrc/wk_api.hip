@@ -331,6 +331,125 @@ wk_status wk_forward(wk_handle* h, const void* d_audio, int32_t dtype, int64_t b
                       h ? h->d_err : nullptr);
 }
 
+// ---------------------------------------------------------------------------
+// wk_scan: every window [w*hop, w*hop + 16000) of long recordings.
+// ---------------------------------------------------------------------------
+namespace {
+
+constexpr int64_t kScanMaxSamples = (int64_t)1 << 30;
+constexpr int64_t kScanChunkWindows = 65536;                  // default windows per chunk (215 MB of features)
+constexpr size_t kScanFeatBytes = sizeof(float) * 13 * 63;    // 3276 B of features per window
+
+struct ScanPlan {
+  int64_t W;           // windows per recording
+  bool shared;         // hop = 256k, k <= kScanMaxK: interior frames computed once per recording
+  int k;
+  int G, g_pad;        // global frames 1..G; frame-store pitch (column g, a multiple of 64 above G)
+  size_t store_bytes;  // frame store [n_rec][13][g_pad], rounded up to 256 B
+};
+
+ScanPlan scan_plan(int64_t n_rec, int64_t n_samples, int32_t hop) {
+  ScanPlan p = {};
+  p.W = n_samples < WK_WIN_SAMPLES ? 0 : (n_samples - WK_WIN_SAMPLES) / hop + 1;
+  p.shared = p.W > 0 && n_rec > 0 && hop % 256 == 0 && hop / 256 <= wk::kScanMaxK;
+  if (p.shared) {
+    p.k = hop / 256;
+    p.G = (int)(p.k * (p.W - 1) + 61);
+    p.g_pad = (p.G + 1 + 63) & ~63;
+    p.store_bytes = ((size_t)n_rec * 13 * p.g_pad * sizeof(float) + 255) & ~(size_t)255;
+  }
+  return p;
+}
+
+wk_status scan_check_geometry(int64_t n_rec, int64_t n_samples, int32_t hop) {
+  if (hop < 1) return invalid("wk_scan: hop < 1");
+  if (n_rec < 0) return invalid("wk_scan: n_rec < 0");
+  if (n_samples < 0 || n_samples > kScanMaxSamples) return invalid("wk_scan: n_samples outside [0, 2^30]");
+  return WK_OK;
+}
+
+}  // namespace
+
+wk_status wk_scan_workspace_bytes(int64_t n_rec, int64_t n_samples, int32_t hop, int64_t windows_per_chunk,
+                                  size_t* bytes) {
+  if (!bytes) return invalid("wk_scan_workspace_bytes: null bytes");
+  *bytes = 0;
+  wk_status s = scan_check_geometry(n_rec, n_samples, hop);
+  if (s != WK_OK) return s;
+  if (windows_per_chunk < 0) return invalid("wk_scan_workspace_bytes: windows_per_chunk < 0");
+  const ScanPlan p = scan_plan(n_rec, n_samples, hop);
+  if (!p.shared) return WK_OK;   // forwarded to the wk_forward path: no workspace
+  const int64_t total = n_rec * p.W;
+  int64_t wpc = windows_per_chunk ? windows_per_chunk : kScanChunkWindows;
+  if (wpc > total) wpc = total;
+  *bytes = p.store_bytes + (size_t)wpc * kScanFeatBytes;
+  return WK_OK;
+}
+
+wk_status wk_scan(wk_handle* h, const void* d_audio, int32_t dtype, int64_t n_rec, int64_t n_samples,
+                  int64_t rec_stride, int32_t hop, float* d_logits, float* d_feats_or_null, void* d_workspace,
+                  size_t workspace_bytes, void* stream) {
+  if (!h) return invalid("wk_scan: null handle");
+  if (h->cfg.mode != WK_MODE_TORCHAUDIO_CMVN) {
+    g_last_error = "wk_scan: the xiaoa CNN consumes mode-B (torchaudio+CMVN) features";
+    return WK_ERR_UNSUPPORTED;
+  }
+  if (!h->d_weights) return invalid("wk_scan: handle created without weights");
+  wk_status s = scan_check_geometry(n_rec, n_samples, hop);
+  if (s != WK_OK) return s;
+  if (dtype != WK_DTYPE_F32 && dtype != WK_DTYPE_I16) return invalid("wk_scan: bad dtype");
+  if (n_rec > 1 && rec_stride < n_samples) return invalid("wk_scan: rec_stride < n_samples");
+  const ScanPlan p = scan_plan(n_rec, n_samples, hop);
+  if (p.W == 0 || n_rec == 0) return WK_OK;
+  if (!d_audio || !d_logits) return invalid("wk_scan: null audio / logits");
+  const bool i16 = dtype == WK_DTYPE_I16;
+  const size_t esz = i16 ? 2 : 4;
+  if (!p.shared) {
+    // No frame of one window is a frame of another: the sliding wk_forward, per recording.
+    for (int64_t r = 0; r < n_rec; ++r) {
+      s = forward_impl(h, (const char*)d_audio + (size_t)(r * rec_stride) * esz, dtype, p.W, WK_WIN_SAMPLES, hop,
+                       d_logits + r * p.W, d_feats_or_null ? d_feats_or_null + r * p.W * 13 * 63 : nullptr, stream,
+                       h->d_err);
+      if (s != WK_OK) return s;
+    }
+    return WK_OK;
+  }
+  const int64_t total = n_rec * p.W;
+  if (!d_workspace || workspace_bytes < p.store_bytes + kScanFeatBytes)
+    return invalid("wk_scan: workspace smaller than wk_scan_workspace_bytes(..., 1 window per chunk)");
+  int64_t wpc = (int64_t)((workspace_bytes - p.store_bytes) / kScanFeatBytes);
+  if (wpc > total) wpc = total;
+  // Chunks are whole work units of wpu consecutive windows of one recording
+  // (the last unit of a recording may hold fewer), contiguous in the flat
+  // [n_rec][W] order, so each chunk is one CNN launch.
+  const int wpu = (int)(wpc < wk::kScanUnitWindows ? wpc : wk::kScanUnitWindows);
+  const int64_t units_per_rec = (p.W + wpu - 1) / wpu;
+  const int64_t n_units = n_rec * units_per_rec;
+  const int64_t units_per_chunk = wpc / wpu;
+  auto flat_of = [&](int64_t u) { return (u / units_per_rec) * p.W + (u % units_per_rec) * wpu; };
+  float* store = (float*)d_workspace;
+  float* chunk_feats = (float*)((char*)d_workspace + p.store_bytes);
+  const hipStream_t st = (hipStream_t)stream;
+  const bool int8 = h->cfg.precision == WK_PREC_INT8;
+  return on_device(h->cfg.device, [&]() -> wk_status {
+    hipError_t e = wk::launch_scan_frames(i16, d_audio, n_rec, rec_stride, p.G, p.g_pad, store, 2 * h->n_cu, st);
+    if (e != hipSuccess) return hip_fail(e, "scan frames launch");
+    for (int64_t u0 = 0; u0 < n_units; u0 += units_per_chunk) {
+      const int64_t u1 = u0 + units_per_chunk < n_units ? u0 + units_per_chunk : n_units;
+      const int64_t flat0 = flat_of(u0), n = (u1 == n_units ? total : flat_of(u1)) - flat0;
+      float* feats = d_feats_or_null ? d_feats_or_null + flat0 * 13 * 63 : chunk_feats;
+      e = wk::launch_scan_assemble(i16, d_audio, rec_stride, hop, p.W, wpu, u0, u1 - u0, flat0, p.g_pad, store,
+                                   feats, 2 * h->n_cu, st);
+      if (e != hipSuccess) return hip_fail(e, "scan assemble launch");
+      e = int8 ? wk::launch_int8_cnn(feats, n, h->d_int8, d_logits + flat0, 4 * h->n_cu, st)
+               : wk::launch_cnn_fused(feats, n, h->d_packed, h->d_bf16, conv_mode_of(h), d_logits + flat0, h->n_cu, st,
+                                      h->d_err);
+      if (e != hipSuccess) return hip_fail(e, "cnn launch");
+    }
+    return WK_OK;
+  });
+}
+
 wk_status wk_synth_clips(uint32_t seed, int64_t first, int64_t count, int32_t n, float* d_out, void* stream) {
   if (count < 0 || n <= 0 || (count > 0 && !d_out)) return invalid("wk_synth_clips: bad arguments");
   hipError_t e = wk::launch_synth(seed, first, count, n, d_out, (hipStream_t)stream);

@@ -69,9 +69,12 @@ __device__ __forceinline__ int refl_idx(int i, int n) {
 
 // GENERAL (wave-uniform) = this wave-round holds an edge frame: per-lane
 // reflected indices.  Otherwise the 21 loads share one offset VGPR.
+// off (GENERAL only): the frame's clip starts `off` samples into the resource
+// (wk_scan.hip: the lane groups of one wave hold edge frames of different
+// windows of one recording); indices are reflected within the clip first.
 template <bool MODE_B, typename T>
 __device__ __forceinline__ void load_raw(__amdgpu_buffer_rsrc_t rs, int base, int j, int n, bool act, bool general,
-                                         Raw<T>& r) {
+                                         Raw<T>& r, int off = 0) {
   if (!act) return;
   if (!general) {
     const int v0 = base + 2 * j;
@@ -82,11 +85,11 @@ __device__ __forceinline__ void load_raw(__amdgpu_buffer_rsrc_t rs, int base, in
 #pragma unroll
     for (int n1 = 0; n1 < 10; ++n1) {
       const int i0 = base + 32 * n1 + 2 * j;
-      r.x0[n1] = raw_ld<T>(rs, MODE_B ? refl_idx(i0, n) : i0);
-      r.x1[n1] = raw_ld<T>(rs, MODE_B ? refl_idx(i0 + 1, n) : i0 + 1);
+      r.x0[n1] = raw_ld<T>(rs, off + (MODE_B ? refl_idx(i0, n) : i0));
+      r.x1[n1] = raw_ld<T>(rs, off + (MODE_B ? refl_idx(i0 + 1, n) : i0 + 1));
     }
     const int ib = j == 15 ? base + 32 * 9 + 32 : base - 1;
-    r.xb = raw_ld<T>(rs, MODE_B ? refl_idx(ib, n) : ib);
+    r.xb = raw_ld<T>(rs, off + (MODE_B ? refl_idx(ib, n) : ib));
   }
 }
 

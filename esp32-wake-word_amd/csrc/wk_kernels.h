@@ -34,6 +34,21 @@ hipError_t launch_frontend(bool mode_b, bool i16, const void* audio, int64_t bat
                            int64_t clip_stride, float* out, int esp_pack, int cmvn, int grid_cap,
                            float pre_emphasis, hipStream_t stream);   // pre_emphasis: 0.97 (mfcc.c:445), 0 = none
 
+// Shared-frame scan (wk_scan.hip), mode B, hop = 256k with k <= kScanMaxK.
+// launch_scan_frames: raw MFCC of global frames 1..G of each of n_rec
+// recordings -> store [n_rec][13][g_pad], frame g at column g (g_pad > G).
+// launch_scan_assemble: units [unit0, unit0 + n_units) of <= wpu (<= kScanUnitWindows)
+// consecutive windows of one recording each, ceil(W / wpu) units per recording:
+// edge frames 0 and 62 of every window + frames 1..61 from the store + CMVN ->
+// feats + (flat window index - flat0) * 819, flat index = rec * W + w.
+constexpr int kScanMaxK = 61;          // beyond it consecutive windows share no interior frame
+constexpr int kScanUnitWindows = 31;   // 62 edge frames per work unit
+hipError_t launch_scan_frames(bool i16, const void* audio, int64_t n_rec, int64_t rec_stride, int G, int g_pad,
+                              float* store, int grid_cap, hipStream_t stream);
+hipError_t launch_scan_assemble(bool i16, const void* audio, int64_t rec_stride, int hop, int64_t W, int wpu,
+                                int64_t unit0, int64_t n_units, int64_t flat0, int g_pad, const float* store,
+                                float* feats, int grid_cap, hipStream_t stream);
+
 // Fused front-end + CNN (wk_fused.hip), mode B only.
 // w = fp32 fragment-major weights (pack_fragments); wbf = bf16 conv fragments
 // (pack_fragments_bf16; hi then lo parts for split bf16) for conv_mode 1

@@ -32,7 +32,7 @@ EXPORTS = ("wk_create", "wk_destroy", "wk_mfcc", "wk_cnn", "wk_forward", "wk_syn
            "wk_wav_read", "wk_wav_load_batch", "wk_augment", "flow_extract_mfcc_single_frame", "wk_device_cmvn",
            "wk_check_device_errors", "wk_ctc_frame_argmax", "wk_record_front", "wk_quantize_frames",
            "wk_ctc_profile", "wk_ctc_stage_times", "wk_ctc_transcribe", "wk_esp_mfcc_create", "wk_esp_mfcc_run",
-           "wk_esp_mfcc_destroy")
+           "wk_esp_mfcc_destroy", "wk_scan", "wk_scan_workspace_bytes")
 
 
 class WkConfig(C.Structure):
@@ -98,6 +98,9 @@ def _declare(L):
     L.wk_augment.argtypes = [vp, i32, C.c_float, C.c_float, C.c_float, u32, vp, i32]
     L.wk_device_cmvn.argtypes = [vp, i32, i64, vp, vp, vp]
     L.wk_check_device_errors.argtypes = [vp, C.POINTER(u32)]
+    if hasattr(L, "wk_scan"):   # (absent from older libraries loaded for A/B timing)
+        L.wk_scan_workspace_bytes.argtypes = [i64, i64, i32, i64, C.POINTER(C.c_size_t)]
+        L.wk_scan.argtypes = [vp, vp, i32, i64, i64, i64, i32, vp, vp, vp, C.c_size_t, vp]
     if hasattr(L, "wk_esp_mfcc_create"):   # (absent from pre-round-4 libraries loaded for A/B timing)
         L.wk_esp_mfcc_create.argtypes = [i32, i32, i32, i32, i32, i32, i32, C.POINTER(vp)]
         L.wk_esp_mfcc_run.argtypes = [vp, vp, i64, i32, i64, i32, C.c_float, vp, vp]
@@ -107,7 +110,8 @@ def _declare(L):
                  "wk_ctc_destroy", "wk_ctc_features", "wk_ctc_forward", "wk_wav_read", "wk_wav_load_batch",
                  "wk_augment", "wk_device_cmvn", "wk_ctc_frame_argmax", "wk_record_front",
                  "wk_quantize_frames", "wk_ctc_profile", "wk_ctc_stage_times", "wk_ctc_transcribe",
-                 "wk_esp_mfcc_create", "wk_esp_mfcc_run", "wk_esp_mfcc_destroy"):
+                 "wk_esp_mfcc_create", "wk_esp_mfcc_run", "wk_esp_mfcc_destroy", "wk_scan",
+                 "wk_scan_workspace_bytes"):
         if hasattr(L, name):
             getattr(L, name).restype = i32
 

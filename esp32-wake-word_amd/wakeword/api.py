@@ -224,6 +224,46 @@ class KWSModel:
                                _stream(torch, x.device)), "wk_forward")
         return (out, feats) if return_features else out
 
+    def scan(self, audio, hop: int = 256, return_features: bool = False, windows_per_chunk: int = 0):
+        """Score every window [w*hop, w*hop + 16000) of a long recording (wk_scan).
+
+        audio (n,) or (R, n) float32/int16, numpy or torch -> logits (W,) or
+        (R, W) on device, W = (n - 16000) // hop + 1 (0 if n < 16000), and the
+        (.., W, 13, 63) features too if asked.  Each result is what ``detect``
+        gives for that window; for hop a multiple of 256 the interior MFCC
+        frames are computed once per recording instead of once per window
+        (wakeword.scan.plan).  windows_per_chunk sizes the workspace (0 = the
+        library default)."""
+        torch = _torch()
+        is_i16 = (isinstance(audio, np.ndarray) and audio.dtype == np.int16) or \
+            (hasattr(audio, "dtype") and str(audio.dtype) == "torch.int16")
+        x = _as_device(audio, torch.int16 if is_i16 else torch.float32, f"cuda:{self.device}")
+        squeeze = x.dim() == 1
+        if squeeze:
+            x = x.unsqueeze(0)
+        if x.dim() != 2:
+            raise ValueError(f"expected audio (n,) or (R, n), got {tuple(x.shape)}")
+        R, n = x.shape
+        if hop < 1:
+            raise ValueError("hop must be >= 1")
+        W = (n - 16000) // hop + 1 if n >= 16000 else 0
+        out = torch.empty((R, W), dtype=torch.float32, device=x.device)
+        feats = torch.empty((R, W, 13, 63), dtype=torch.float32, device=x.device) if return_features else None
+        nbytes = C.c_size_t(0)
+        check(lib().wk_scan_workspace_bytes(R, n, hop, windows_per_chunk, C.byref(nbytes)), "wk_scan_workspace_bytes")
+        ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=x.device) if nbytes.value else None
+        check(lib().wk_scan(self._h.h, C.c_void_p(x.data_ptr()), _lib.WK_DTYPE_I16 if is_i16 else _lib.WK_DTYPE_F32,
+                            R, n, n, hop, C.c_void_p(out.data_ptr()),
+                            C.c_void_p(feats.data_ptr()) if feats is not None else None,
+                            C.c_void_p(ws.data_ptr()) if ws is not None else None, nbytes.value,
+                            _stream(torch, x.device)), "wk_scan")
+        # (ws is released to torch's caching allocator here; the allocator hands
+        # it out again only in this stream's order, after the scan's launches)
+        if squeeze:
+            out = out[0]
+            feats = feats[0] if feats is not None else None
+        return (out, feats) if return_features else out
+
     def probability(self, audio):
         return _torch().sigmoid(self.detect(audio))
 

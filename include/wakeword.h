@@ -117,6 +117,46 @@ wk_status wk_cnn(wk_handle* h, const float* d_feats, int64_t batch, float* d_log
 wk_status wk_forward(wk_handle* h, const void* d_audio, int32_t dtype, int64_t batch, int32_t win_len,
                      int64_t clip_stride, float* d_logits, float* d_feats_or_null, void* stream);
 
+/* ---- Dense sliding-window scan of long recordings ---------------------------
+ * wk_scan scores every window of `n_rec` recordings of `n_samples` samples each
+ * (recording r at d_audio + r*rec_stride elements; f32, or i16 scaled by
+ * 1/32768).  Window w covers samples [w*hop, w*hop + 16000) of its recording;
+ * W = (n_samples - 16000) / hop + 1 windows per recording (0 if n_samples <
+ * 16000; trailing samples that complete no window are ignored; windows never
+ * cross recordings).  The result for a window is what wk_forward gives for the
+ * clip starting there: d_logits [n_rec][W], and the mode-B CMVN'd features
+ * [n_rec][W][13][63] into d_feats_or_null when given.
+ *
+ * When hop is a multiple of 256 (the front-end's frame hop) frames 1..61 of a
+ * window read only samples inside it, so they are frames of the recording
+ * (global frame g = hop/256 * w + t) and are computed once; only frame 0 and
+ * frame 62 (reflection at the window's own edges) are computed per window.
+ * That path needs a caller-owned workspace: the frame store plus the features
+ * of one chunk of windows.  wk_scan_workspace_bytes gives its size for
+ * `windows_per_chunk` windows per chunk (0 = library default); wk_scan derives
+ * the chunk size from workspace_bytes, and a workspace below the size for one
+ * window per chunk is WK_ERR_INVALID_ARG.  Any other hop >= 1 (and a multiple
+ * of 256 above 15616, where consecutive windows share no frame) is forwarded
+ * to the wk_forward path per recording with clip_stride = hop -- bit-identical
+ * to wk_forward; the workspace is unused and its size is 0.
+ *
+ * wk_scan is stream-ordered: it allocates nothing, never blocks the host and
+ * issues all its launches to `stream` in order.  The shared-frame path touches
+ * no handle state, so concurrent scans on several streams (each with its own
+ * workspace) need no ordering.  A forwarded scan is a wk_forward call and
+ * shares what wk_forward shares: on an INT8 (or unfused) handle it stages its
+ * features in the handle's own workspace, whose uses the library orders across
+ * streams with an event, so such scans serialise on the handle.  hop < 1, n_rec < 0, n_samples > 2^30,
+ * n_rec > 1 with rec_stride < n_samples, or a null pointer with W > 0 give
+ * WK_ERR_INVALID_ARG before any device work; W = 0 is WK_OK with no launches.
+ * Handle requirements and the error word are wk_forward's / wk_cnn's. */
+wk_status wk_scan_workspace_bytes(int64_t n_rec, int64_t n_samples, int32_t hop,
+                                  int64_t windows_per_chunk /* 0 = library default */, size_t* bytes);
+wk_status wk_scan(wk_handle* h, const void* d_audio, int32_t dtype, int64_t n_rec, int64_t n_samples,
+                  int64_t rec_stride, int32_t hop, float* d_logits /* [n_rec][W] */,
+                  float* d_feats_or_null /* [n_rec][W][13][63] */,
+                  void* d_workspace, size_t workspace_bytes, void* stream);
+
 /* Device-side synthetic clip generator: fills
  * d_out[count][n] with clips first..first+count-1 of the counter-based
  * generator keyed on `seed` (bit-compatible with oracle.synth_clips up to
