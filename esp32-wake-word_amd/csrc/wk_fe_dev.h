@@ -30,7 +30,8 @@ __device__ __forceinline__ f2 w32(int k2) {
 // a neighbouring lane's value (DPP row rotate), so it is not loaded twice;
 // xb covers the one partner outside the slot (lane 0: x[r(base-1)], lane 15:
 // x[r(i0(9,15)+2)]).  Kept in the input type so the loads stay outstanding
-// until first use.
+// until first use.  (The fused kernel loads r() = identity in every round and
+// rebuilds the reflected rows in registers: load_raw_part, fe_stage0_rows.)
 template <typename T>
 struct Raw {
   T x0[10], x1[10];
@@ -67,8 +68,10 @@ __device__ __forceinline__ int refl_idx(int i, int n) {
   return i > n - 1 ? 2 * (n - 1) - i : i;
 }
 
-// GENERAL (wave-uniform) = this wave-round holds an edge frame: per-lane
-// reflected indices.  Otherwise the 21 loads share one offset VGPR.
+// The loader of the standalone front-end (wk_frontend.hip: any win_len, mode
+// A) and of wk_scan.hip.  GENERAL (wave-uniform) = this wave-round holds an
+// edge frame: per-lane reflected indices, 21 single loads.  Otherwise the 10
+// pair loads + xb share one offset VGPR.
 // off (GENERAL only): the frame's clip starts `off` samples into the resource
 // (wk_scan.hip: the lane groups of one wave hold edge frames of different
 // windows of one recording); indices are reflected within the clip first.
@@ -93,28 +96,28 @@ __device__ __forceinline__ void load_raw(__amdgpu_buffer_rsrc_t rs, int base, in
   }
 }
 
-// Part k (0..3) of load_raw: rows n1 with pf_part(n1) == k (and xb with part
-// 0), so a round's prefetch can be spread over the round instead of issued as
-// one burst (eight waves issuing 11 loads each at once filled the TA FIFOs and
-// stalled issue).  The edge-frame (GENERAL) form is issued whole with part 0.
+// Part k (0..3) of the fused kernel's loads: rows n1 with pf_part(n1) == k
+// (and xb with part 0), so a round's prefetch can be spread over the round
+// instead of issued as one burst (eight waves issuing 11 loads each at once
+// filled the TA FIFOs and stalled issue).  Every round issues these same
+// unreflected pair loads, the two edge frames (0 and 62) included: their
+// reflected rows repeat samples that other rows of the same frame hold, and
+// fe_stage0_rows takes them from there (the rows' own loads fall outside the
+// clip and return 0).  The one sample no row holds, x[160] for frame 0, comes
+// in xb (xb_idx; base - 1 for every other frame).
 // The packed unit front-loads the parts (rows 0-3, 4-6, 7-8, 9) and issues
 // them earlier in the round (fe_rest); the scalar unit issues rows 3k..3k+2.
 __device__ __forceinline__ constexpr int pf_part(int n1) {
   return WK_FE_STAGED ? n1 / 3 : (n1 < 4 ? 0 : n1 < 7 ? 1 : n1 < 9 ? 2 : 3);
 }
-template <bool MODE_B, typename T>
-__device__ __forceinline__ void load_raw_part(__amdgpu_buffer_rsrc_t rs, int base, int j, int n, bool act,
-                                              bool general, Raw<T>& r, int part) {
-  if (!act) return;
-  if (general) {
-    if (part == 0) load_raw<MODE_B, T>(rs, base, j, n, act, true, r);
-    return;
-  }
+template <typename T>
+__device__ __forceinline__ void load_raw_part(__amdgpu_buffer_rsrc_t rs, int base, int xb_idx, int j, Raw<T>& r,
+                                              int part) {
   const int v0 = base + 2 * j;
 #pragma unroll
   for (int n1 = 0; n1 < 10; ++n1)
     if (pf_part(n1) == part) raw_ld2<T>(rs, v0 + 32 * n1, r.x0[n1], r.x1[n1]);
-  if (part == 0) r.xb = raw_ld<T>(rs, base - 1);
+  if (part == 0) r.xb = raw_ld<T>(rs, xb_idx);
 }
 
 struct NoPrefetch {
@@ -169,6 +172,9 @@ __device__ __forceinline__ void fe_init_tws(float* tws, int tid, int nthreads) {
 //   y[i] = x[i] - 0.97 x[i-1], y[0] = x[0]   (torchaudio preemphasis / mfcc.c:66-74)
 // On reflected rows (mode B edge frames) y(i0) = x[r] - 0.97 x[r-1] pairs
 // each sample with the NEXT one: own x1 for y0, the next lane's x0 for y1.
+// This form serves load_raw's GENERAL loads (wk_frontend.hip, wk_scan.hip:
+// any clip length, edge frames of several windows in one wave); the fused
+// kernel's stage 0 is fe_stage0_fused below.
 template <bool MODE_B, typename T>
 __device__ __forceinline__ void fe_stage0(const Raw<T>& raw, int base, int n, int j, bool general,
                                           const FeTables& tb, f2 (&a)[16], float pre = -0.97f WK_SP_PARAM) {
@@ -215,6 +221,92 @@ __device__ __forceinline__ void fe_stage0(const Raw<T>& raw, int base, int n, in
 #pragma unroll
     for (int n1 = 0; n1 < 10; ++n1) a[n1] = f2{y0[n1], y1[n1]} * w[n1];
   }
+#pragma unroll
+  for (int n1 = 10; n1 < 16; ++n1) a[n1] = f2{0.0f, 0.0f};
+}
+
+// Stage 0 of the fused kernel (mode B, 16,000-sample clips, Raw filled by
+// load_raw_part).  EDGE, wave-uniform: 0 = no edge frame in this wave-round,
+// 1 = lane group 0 holds frame 0, 2 = lane group 3 holds frame 62.  The
+// centre padding reflects whole rows (tests/test_edge_frame_rows.py):
+//   frame 0  (base -160):  rows 0-4 reflected, r0 = r(i0) = 160 - 32 n1 - 2 j;
+//                          rows 5-9 hold x[0..159] unreflected, i0 == 0 is row 5 lane 0
+//   frame 62 (base 15712): row 9 reflected, r0 = 15998 - 2 j; row 8 holds x[15968..15999]
+// and a reflected row needs y(i0) = fma(pre, x[r0-1], x[r0]), y(i0+1) =
+// fma(pre, x[r0-2], x[r0-1]).  Those samples sit in the frame's own registers:
+//   frame 0:  (x[r0-2], x[r0-1]) is the pair of row 9 - n1, lane 15 - j (row_mirror);
+//             x[r0] is the first of row 9 - n1, lane 16 - j (row_shr:1 of the
+//             mirrored firsts); lane 0 takes the first of its row 10 - n1, xb = x[160] for row 0
+//   frame 62: x[r0] is the first of row 8, lane 15 - j (row_mirror); (x[r0-2],
+//             x[r0-1]) is the pair of row 8, lane 14 - j (row_shl:1 of the
+//             mirrored pair); lane 15 takes its own row-7 pair (x[15966], x[15967])
+// The DPP moves write the edge frame's lane group only (row_mask) and leave
+// the other groups' operands in place, so each row is still the common two
+// FMAs and the window multiply: no second loop, no per-sample index or
+// select, and the same FMA forms as the per-lane reflected loads gave
+// (fe_stage0's GENERAL path, which wk_scan.hip and wk_frontend.hip keep).
+template <int CTRL, int ROWS>
+__device__ __forceinline__ float dpp_rows(float old, float src) {   // rows outside ROWS, lanes without a source: old
+  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(src), CTRL, ROWS, 0xF, false));
+}
+template <int EDGE, typename T>
+__device__ __forceinline__ void fe_stage0_rows(const Raw<T>& raw, int lane, const f2 (&w)[10], f2 (&a)[16],
+                                               float pre) {
+  const int j = lane & 15;
+  float prev_rot = 0.0f;
+#pragma unroll
+  for (int n1 = 0; n1 < 10; ++n1) {
+    const float x0 = to_f(raw.x0[n1]), x1 = to_f(raw.x1[n1]);
+    // x[i0-1]: lane j-1's x1 of this row; lane 0 takes lane 15's x1 of the previous row.
+    // DPP moves read other lanes: they must execute with the whole row
+    // active, so they are materialised (asm barrier) before any lane select.
+    float rot = row_ror1(x1);
+    asm volatile("" : "+v"(rot));
+    const float xm = j != 0 ? rot : (n1 == 0 ? to_f(raw.xb) : prev_rot);
+    prev_rot = rot;
+    // y0 = fma(pre, pm, c0), y1 = fma(pre, p1, c1)
+    float c0 = x0, c1 = x1, pm = xm, p1 = x0;
+    if constexpr (EDGE == 1) {
+      if (n1 < 5) {
+        const float m0 = to_f(raw.x0[9 - n1]), m1 = to_f(raw.x1[9 - n1]);
+        p1 = dpp_rows<0x140, 0x1>(x0, m0);   // x[r0-2]
+        c1 = dpp_rows<0x140, 0x1>(x1, m1);   // x[r0-1]
+        pm = dpp_rows<0x140, 0x1>(xm, m1);
+        asm volatile("" : "+v"(p1), "+v"(c1), "+v"(pm));
+        const float l0 = n1 == 0 ? to_f(raw.xb) : to_f(raw.x0[10 - n1]);
+        c0 = dpp_rows<0x111, 0x1>(lane == 0 ? l0 : x0, p1);   // x[r0]
+        asm volatile("" : "+v"(c0));
+      }
+    } else if constexpr (EDGE == 2) {
+      if (n1 == 9) {
+        const float q0 = to_f(raw.x0[8]), q1 = to_f(raw.x1[8]);
+        c0 = dpp_rows<0x140, 0x8>(x0, q0);          // x[r0]
+        float s1 = dpp_rows<0x140, 0x8>(x1, q1);    // x[r0+1]
+        asm volatile("" : "+v"(c0), "+v"(s1));
+        p1 = dpp_rows<0x101, 0x8>(lane == 63 ? to_f(raw.x0[7]) : x0, c0);   // x[r0-2]
+        c1 = dpp_rows<0x101, 0x8>(lane == 63 ? to_f(raw.x1[7]) : x1, s1);   // x[r0-1]
+        asm volatile("" : "+v"(p1), "+v"(c1));
+        pm = lane >= 48 ? c1 : xm;
+      }
+    }
+    float y0 = __builtin_fmaf(pre, pm, c0);   // pre = -0.97
+    const float y1 = __builtin_fmaf(pre, p1, c1);
+    if (EDGE == 1 && n1 == 5) y0 = lane == 0 ? x0 : y0;   // y[0] = x[0]
+    a[n1] = f2{y0, y1} * w[n1];
+  }
+}
+template <typename T>
+__device__ __forceinline__ void fe_stage0_fused(const Raw<T>& raw, int lane, int edge, const FeTables& tb,
+                                                f2 (&a)[16], float pre = -0.97f) {
+  // All ten window pairs are read up front (see fe_stage0).
+  f2 w[10];
+#pragma unroll
+  for (int n1 = 0; n1 < 10; ++n1) w[n1] = *reinterpret_cast<const f2*>(tb.win + 32 * n1 + 2 * (lane & 15));
+  // The windowed pairs are formed in each branch, so the paths merge on a[]
+  // (register pairs), as in fe_stage0.
+  if (edge == 0) fe_stage0_rows<0>(raw, lane, w, a, pre);
+  else if (edge == 1) fe_stage0_rows<1>(raw, lane, w, a, pre);
+  else fe_stage0_rows<2>(raw, lane, w, a, pre);
 #pragma unroll
   for (int n1 = 10; n1 < 16; ++n1) a[n1] = f2{0.0f, 0.0f};
 }

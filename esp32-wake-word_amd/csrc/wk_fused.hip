@@ -61,6 +61,12 @@ constexpr int NBF = 4;               // clips per CNN batch
 #error "WK_FE_WAVES != 8 is a diagnostic build (front-end role alone, WAKEWORD_FUSED_EXP=1)"
 #endif
 constexpr int kFeWaves = WK_FE_WAVES;
+// Round-1 frame slots swapped between waves w and w ^ 4 (fe_role).  The
+// default is each unit's measured choice; -DWK_FE_ROUND1_SWAP=0/1 builds the
+// other one for an A/B (bit-identical either way).
+#ifndef WK_FE_ROUND1_SWAP
+#define WK_FE_ROUND1_SWAP WK_FE_STAGED
+#endif
 constexpr int kFusedBlock = 1024;    // 8 front-end + 8 CNN waves
 // LDS carve after the front-end's (wk_fe_dev.h): fixed tail, then the CNN
 // images [clip][t][ci] -- fp32, or bf16 for bf16 convolutions -- overlaying
@@ -265,15 +271,21 @@ __device__ __forceinline__ void fe_role(float* smem, const T* __restrict__ audio
   // w + 8r + 16(g&1) + 32(g>>1) (groups 0/1 16 frames apart: disjoint LDS
   // banks).  A dynamic hand-out through an LDS counter was measured slower:
   // the atomic's return latency lands on the prefetch path.  Both edge
-  // frames in wave 0's round 0 (one reflected-index round per clip instead
-  // of two) measured -1 %: that wave then finishes last at the clip barrier.
+  // frames in wave 0's round 0 (when an edge round still issued 21 per-lane
+  // reflected loads: one such round per clip instead of two) measured -1 %:
+  // that wave then finishes last at the clip barrier.
   //
   // Prefetch context of a round, built once per round: the clip's buffer
-  // resource and whether the round holds a reflected edge frame (frame 0 in
-  // wave 0 round 0, frame 62 in wave 6 round 1; wave-uniform).  Past the
-  // workgroup's last clip the resource has num_records 0, so those loads
-  // return 0 without a branch; the padding slot (frame 63) needs no lane mask
-  // either, since its samples past the clip's end come back 0 from the same
+  // resource and the lane group's sample offsets.  Every round issues the
+  // same pair loads; the two rounds that hold a reflected edge frame (frame 0
+  // in wave 0 round 0, frame 62 in round 1 of the wave with slot 6;
+  // wave-uniform) differ only in stage 0, which takes the reflected rows from
+  // the frame's other rows by DPP (fe_stage0_rows: +36 / +9 instructions on
+  // the common round; the reflected-index rounds were +280 and held every
+  // wave at the power-row barrier, fp32 +2.2-2.7 %, profiles/edge_rows_ab.md),
+  // and in frame 0's xb.  Past the workgroup's last clip the resource has
+  // num_records 0, so those loads return 0 without a branch; the padding
+  // slot (frame 63) needs no lane mask either, since its samples past the clip's end come back 0 from the same
   // bounds check.  (Rebuilt inside each of the four prefetch parts, the 64-bit
   // clip address, the `i < n_mine` test and the per-lane `frame < 63` exec mask
   // cost ~28 scalar/branch instructions per part, ~13 % of a round's issue.)
@@ -282,32 +294,35 @@ __device__ __forceinline__ void fe_role(float* smem, const T* __restrict__ audio
   constexpr uint32_t kClipBytes = kWinSamples * sizeof(T);
   struct PfCtx {
     __amdgpu_buffer_rsrc_t rs;
-    int base;       // first sample of the lane group's frame (before reflection)
-    bool general;   // edge frame: per-lane reflected indices, issued whole with part 0
+    int base;   // first sample of the lane group's frame (before reflection)
+    int xb;     // the sample before it; frame 0: x[160], the one reflected sample no row holds
   };
   // Frame slot of round r.  The bf16-family unit (scalar front-end) swaps
   // round 1's slots between waves w and w ^ 4, so its second edge frame (62)
   // runs on wave 2 rather than wave 6: waves 4-7 issue after 0-3 on each SIMD
-  // and reach the power-row barrier last, wave 6 with the edge frame latest.
-  // bf16 +0.8 %; the packed fp32 unit measured -0.8 % with it
-  // (profiles/r06ae_round1_swap_ab.txt).  Bit-identical either way.
-  auto fwr = [&](int r) { return FEW == 8 && WK_FE_STAGED && r == 1 ? fw ^ 4 : fw; };
+  // and reach the power-row barrier last.  Tuned when wave 6's edge round
+  // was the slow one (bf16 +0.8 %, packed fp32 unit -0.8 %,
+  // profiles/r06ae_round1_swap_ab.txt) and re-measured with the short edge
+  // rounds: bf16 still +1.5 % with the swap, fp32 +0.1 % (noise) and keeps the
+  // plain mapping (profiles/edge_rows_ab.md).  Bit-identical either way.
+  auto fwr = [&](int r) { return FEW == 8 && WK_FE_ROUND1_SWAP && r == 1 ? fw ^ 4 : fw; };
   auto pf_ctx = [&](const T* p, bool ok, int r) -> PfCtx {
     const int fl = fwr(r) + 8 * r + slot_base;
-    return {make_rsrc(p, ok ? kClipBytes : 0u), 256 * fl - 160, (r == 0 && fwr(r) == 0) || (r == 1 && fwr(r) == 6)};
+    return {make_rsrc(p, ok ? kClipBytes : 0u), 256 * fl - 160, fl == 0 ? 160 : 256 * fl - 161};
   };
 
   Raw<T> pf;
   {
     const PfCtx c0 = pf_ctx(cptr, n_mine > 0, r0);
-    load_raw<true>(c0.rs, c0.base, j, kWinSamples, true, c0.general, pf);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) load_raw_part(c0.rs, c0.base, c0.xb, j, pf, k);
   }
   WK_STAMP_INIT
   for (int64_t i = 0; i < n_mine; ++i) {
 #pragma unroll 1
     for (int r = r0; r <= r1; ++r) {
       const int fl = fwr(r) + 8 * r + slot_base;   // == frame index t (one chunk per clip)
-      const bool general = (r == 0 && fwr(r) == 0) || (r == 1 && fwr(r) == 6);
+      const int edge = r == 0 && fwr(r) == 0 ? 1 : r == 1 && fwr(r) == 6 ? 2 : 0;   // frame 0 / 62 in this wave-round
       f2 a[16];
 #ifdef WK_DIAG
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // diagnostic: time the wait for the prefetched audio apart
@@ -315,7 +330,7 @@ __device__ __forceinline__ void fe_role(float* smem, const T* __restrict__ audio
 #endif
       // Every lane runs the round (the frame-63 slot into a scratch row) so
       // the prefetch parts issued from inside fe_rest load for all lanes.
-      fe_stage0<true>(pf, 256 * fl - 160, kWinSamples, j, general, tb, a);
+      fe_stage0_fused(pf, lane, edge, tb, a);
       WK_STAMP(0);
       // next round: (i, 1) after round 0, (i + 1, 0) after round 1 (one-round waves: (i + 1, r0))
       const PfCtx nx = r < r1 ? pf_ctx(cptr, true, r + 1) : pf_ctx(cptr + step, i + 1 < n_mine, r0);
@@ -325,7 +340,7 @@ __device__ __forceinline__ void fe_role(float* smem, const T* __restrict__ audio
       // the first DFT16 overlap the slower waves' mel.
       auto pf_part = [&](int k) {
         if (k >= 0) {
-          load_raw_part<true>(nx.rs, nx.base, j, kWinSamples, true, nx.general, pf, k);
+          load_raw_part(nx.rs, nx.base, nx.xb, j, pf, k);
         } else if (r == r0) {
           spin_until<kPrioFe>(ctrl, kCtrlFeBar, p_wait);
           WK_STAMP(9);
