@@ -32,7 +32,8 @@ EXPORTS = ("wk_create", "wk_destroy", "wk_mfcc", "wk_cnn", "wk_forward", "wk_syn
            "wk_wav_read", "wk_wav_load_batch", "wk_augment", "flow_extract_mfcc_single_frame", "wk_device_cmvn",
            "wk_check_device_errors", "wk_ctc_frame_argmax", "wk_record_front", "wk_quantize_frames",
            "wk_ctc_profile", "wk_ctc_stage_times", "wk_ctc_transcribe", "wk_esp_mfcc_create", "wk_esp_mfcc_run",
-           "wk_esp_mfcc_destroy", "wk_scan", "wk_scan_workspace_bytes")
+           "wk_esp_mfcc_destroy", "wk_scan", "wk_scan_workspace_bytes", "wk_trainer_create", "wk_trainer_destroy",
+           "wk_trainer_grad", "wk_trainer_step", "wk_trainer_weights")
 
 
 class WkConfig(C.Structure):
@@ -43,6 +44,11 @@ class WkConfig(C.Structure):
 class WkCtcConfig(C.Structure):
     _fields_ = [("vocab", C.c_int32), ("hidden", C.c_int32), ("layers", C.c_int32), ("n_mels", C.c_int32),
                 ("device", C.c_int32), ("precision", C.c_int32)]
+
+
+class WkAdamW(C.Structure):
+    _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
+                ("weight_decay", C.c_float)]
 
 
 class WkWavInfo(C.Structure):
@@ -105,13 +111,20 @@ def _declare(L):
         L.wk_esp_mfcc_create.argtypes = [i32, i32, i32, i32, i32, i32, i32, C.POINTER(vp)]
         L.wk_esp_mfcc_run.argtypes = [vp, vp, i64, i32, i64, i32, C.c_float, vp, vp]
         L.wk_esp_mfcc_destroy.argtypes = [vp]
+    if hasattr(L, "wk_trainer_create"):   # (absent from older libraries loaded for A/B timing)
+        L.wk_trainer_create.argtypes = [i32, vp, C.POINTER(vp)]
+        L.wk_trainer_destroy.argtypes = [vp]
+        L.wk_trainer_grad.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp]
+        L.wk_trainer_step.argtypes = [vp, C.POINTER(WkAdamW), vp, vp]
+        L.wk_trainer_weights.argtypes = [vp, vp, vp]
     for name in ("wk_create", "wk_destroy", "wk_mfcc", "wk_cnn", "wk_forward", "wk_synth_clips", "wk_normalize",
                  "wk_stream_create", "wk_stream_destroy", "wk_stream_reset", "wk_stream_push", "wk_ctc_create",
                  "wk_ctc_destroy", "wk_ctc_features", "wk_ctc_forward", "wk_wav_read", "wk_wav_load_batch",
                  "wk_augment", "wk_device_cmvn", "wk_ctc_frame_argmax", "wk_record_front",
                  "wk_quantize_frames", "wk_ctc_profile", "wk_ctc_stage_times", "wk_ctc_transcribe",
                  "wk_esp_mfcc_create", "wk_esp_mfcc_run", "wk_esp_mfcc_destroy", "wk_scan",
-                 "wk_scan_workspace_bytes"):
+                 "wk_scan_workspace_bytes", "wk_trainer_create", "wk_trainer_destroy", "wk_trainer_grad",
+                 "wk_trainer_step", "wk_trainer_weights"):
         if hasattr(L, name):
             getattr(L, name).restype = i32
 

@@ -336,6 +336,34 @@ wk_status wk_wav_load_batch(const char* const* paths, int32_t n, int32_t pad_to,
 wk_status wk_augment(const float* in, int32_t n, float speed, float volume, float noise_level, uint32_t seed, float* out,
                      int32_t out_len);
 
+/* ---- Training step (ml_models/main.py:13-64, train_model) --------------------
+ * LightweightKWS(num_classes=1) under BCEWithLogitsLoss and AdamW, fp32.  A
+ * wk_trainer owns the weights (blob order of WK_NUM_WEIGHTS), the last
+ * gradients, AdamW's moments and step count, and a workspace of per-workgroup
+ * gradient sums that grows on the first call with a larger batch (the only
+ * time a call blocks the host): issue one trainer's calls on one stream.
+ * Gradients are reduced in a fixed order without atomics, so the same inputs
+ * give the same bits.  ReLU has gradient 0 at a pre-activation <= 0; a
+ * max-pool pair sends its gradient to the larger element, the first on an
+ * exact tie (torch's conventions). */
+typedef struct wk_trainer wk_trainer;
+typedef struct { float lr, beta1, beta2, eps, weight_decay; } wk_adamw;   /* main.py:16-22: 5e-4, .9, .99, 1e-7, 1e-3 */
+
+wk_status wk_trainer_create(int32_t device, const float* host_weights /* WK_NUM_WEIGHTS */, wk_trainer** out);
+wk_status wk_trainer_destroy(wk_trainer* t);
+
+/* d_feats [batch][13][63], d_labels [batch] (0/1 floats) -> mean BCE-with-logits loss (*d_loss),
+ * logits [batch] and gradients [WK_NUM_WEIGHTS] (either may be NULL); the gradients are also kept in the trainer. */
+wk_status wk_trainer_grad(wk_trainer* t, const float* d_feats, const float* d_labels, int64_t batch,
+                          float* d_loss, float* d_logits_or_null, float* d_grads_or_null, void* stream);
+
+/* One AdamW step with the trainer's last gradients, or with d_grads_or_null [WK_NUM_WEIGHTS] when given
+ * (data-parallel callers average per-rank gradients themselves and pass the result). */
+wk_status wk_trainer_step(wk_trainer* t, const wk_adamw* opt, const float* d_grads_or_null, void* stream);
+
+/* Current weights, blob order, device to device, stream-ordered. */
+wk_status wk_trainer_weights(wk_trainer* t, float* d_out, void* stream);
+
 /* Human-readable text for a status / the last HIP error seen by this thread. */
 const char* wk_status_string(wk_status s);
 const char* wk_last_error(void);
