@@ -28,7 +28,10 @@ struct wk_handle {
   float* d_weights;      // packed WK_NUM_WEIGHTS floats, or nullptr (front-end only handle)
   float* d_packed;       // fragment-major weights (wk::pack_fragments) for the fused kernel
   float* d_feats_ws;     // feature workspace for the unfused path
-  int8_t* d_int8;        // int8 weights (WK_PREC_INT8, wk::quantize_int8_weights)
+  int8_t* d_int8;        // int8 weights (WK_PREC_INT8, wk::quantize_int8_weights at quant.e_w)
+  std::vector<float> h_w;    // host copy of the fp32 weights (wk_set_quant re-quantises them, wk_calibrate ranges them)
+  wk_quant_spec quant;       // WK_PREC_INT8: the spec in force (wk_set_quant; default xiaoa.info's) ...
+  wk::Int8Params qp;         // ... and what the int8 kernels take from it
   uint16_t* d_bf16;      // bf16 conv fragments (WK_PREC_BF16; BF16X3: hi then lo, wk::pack_fragments_bf16)
   int64_t ws_clips;
   int unfused;           // WAKEWORD_UNFUSED=1: front-end + CNN as two kernels (A/B testing)
@@ -102,6 +105,8 @@ wk_status wk_create(const wk_config* cfg, const float* host_weights, wk_handle**
   wk_handle* h = new (std::nothrow) wk_handle();
   if (!h) return WK_ERR_NO_MEMORY;
   h->cfg = *cfg;
+  wk_quant_spec_default(&h->quant);
+  (void)wk::int8_params(h->quant, &h->qp);
   {
     const char* u = getenv("WAKEWORD_UNFUSED");
     h->unfused = u && u[0] == '1';
@@ -125,6 +130,7 @@ wk_status wk_create(const wk_config* cfg, const float* host_weights, wk_handle**
     if ((e2 = hipEventCreateWithFlags(&h->ws_free, hipEventDisableTiming)) != hipSuccess)
       return hip_fail(e2, "hipEventCreate");
     if (host_weights) {
+      h->h_w.assign(host_weights, host_weights + WK_NUM_WEIGHTS);
       if ((e2 = hipMalloc(&h->d_weights, sizeof(float) * WK_NUM_WEIGHTS)) != hipSuccess)
         return hip_fail(e2, "hipMalloc(weights)");
       if ((e2 = hipMemcpy(h->d_weights, host_weights, sizeof(float) * WK_NUM_WEIGHTS, hipMemcpyHostToDevice)) !=
@@ -148,7 +154,7 @@ wk_status wk_create(const wk_config* cfg, const float* host_weights, wk_handle**
       }
       if (cfg->precision == WK_PREC_INT8) {
         std::vector<int8_t> q(wk::kNumInt8Weights);
-        wk::quantize_int8_weights(host_weights, q.data());
+        wk::quantize_int8_weights(host_weights, h->quant.e_w, q.data());
         if ((e2 = hipMalloc(&h->d_int8, q.size())) != hipSuccess) return hip_fail(e2, "hipMalloc(int8 weights)");
         if ((e2 = hipMemcpy(h->d_int8, q.data(), q.size(), hipMemcpyHostToDevice)) != hipSuccess)
           return hip_fail(e2, "hipMemcpy(int8 weights)");
@@ -238,7 +244,7 @@ wk_status wk_cnn(wk_handle* h, const float* d_feats, int64_t batch, float* d_log
   if (batch < 0 || (batch > 0 && (!d_feats || !d_logits))) return invalid("wk_cnn: bad arguments");
   return on_device(h->cfg.device, [&]() -> wk_status {
     hipError_t e = h->cfg.precision == WK_PREC_INT8
-                       ? wk::launch_int8_cnn(d_feats, batch, h->d_int8, d_logits, 4 * h->n_cu, (hipStream_t)stream)
+                       ? wk::launch_int8_cnn(d_feats, batch, h->d_int8, h->qp, d_logits, 4 * h->n_cu, (hipStream_t)stream)
                        : wk::launch_cnn_fused(d_feats, batch, h->d_packed, h->d_bf16, conv_mode_of(h), d_logits, h->n_cu,
                                               (hipStream_t)stream, h->d_err);
     return e == hipSuccess ? WK_OK : hip_fail(e, "cnn launch");
@@ -314,7 +320,7 @@ static wk_status forward_impl(wk_handle* h, const void* d_audio, int32_t dtype, 
       hipError_t e = wk::launch_frontend(true, dtype == WK_DTYPE_I16, a, n, win_len, clip_stride, feats, 0, 1,
                                          2 * h->n_cu, 0.97f, (hipStream_t)stream);
       if (e != hipSuccess) return hip_fail(e, "frontend launch");
-      e = int8 ? wk::launch_int8_cnn(feats, n, h->d_int8, d_logits + c0, 4 * h->n_cu, (hipStream_t)stream)
+      e = int8 ? wk::launch_int8_cnn(feats, n, h->d_int8, h->qp, d_logits + c0, 4 * h->n_cu, (hipStream_t)stream)
                : wk::launch_cnn_fused(feats, n, h->d_packed, h->d_bf16, conv_mode_of(h), d_logits + c0, h->n_cu,
                                       (hipStream_t)stream, d_err);
       if (e != hipSuccess) return hip_fail(e, "cnn launch");
@@ -441,13 +447,133 @@ wk_status wk_scan(wk_handle* h, const void* d_audio, int32_t dtype, int64_t n_re
       e = wk::launch_scan_assemble(i16, d_audio, rec_stride, hop, p.W, wpu, u0, u1 - u0, flat0, p.g_pad, store,
                                    feats, 2 * h->n_cu, st);
       if (e != hipSuccess) return hip_fail(e, "scan assemble launch");
-      e = int8 ? wk::launch_int8_cnn(feats, n, h->d_int8, d_logits + flat0, 4 * h->n_cu, st)
+      e = int8 ? wk::launch_int8_cnn(feats, n, h->d_int8, h->qp, d_logits + flat0, 4 * h->n_cu, st)
                : wk::launch_cnn_fused(feats, n, h->d_packed, h->d_bf16, conv_mode_of(h), d_logits + flat0, h->n_cu, st,
                                       h->d_err);
       if (e != hipSuccess) return hip_fail(e, "cnn launch");
     }
     return WK_OK;
   });
+}
+
+// ---------------------------------------------------------------------------
+// Post-training int8 quantisation: the spec, and calibration's host step.
+// ---------------------------------------------------------------------------
+namespace {
+
+// b(a) = min{e : a <= 127 * 2^e} from the float's bits, clamped to [-24, 7]: 127 * 2^e = 1.984375 * 2^(e + 6),
+// mantissa field 0x7E0000, so with exponent field E it is E - 6 up to that mantissa and E - 5 above it.
+// (wk_quant.hip's kernel bins with the same rule.)
+int hold_exp(float a) {
+  uint32_t u;
+  memcpy(&u, &a, 4);
+  u &= 0x7FFFFFFFu;
+  const int b = (int)(u >> 23) - 127 - ((u & 0x7FFFFFu) <= 0x7E0000u ? 6 : 5);
+  return u == 0 || b < -24 ? -24 : (b > 7 ? 7 : b);
+}
+
+}  // namespace
+
+wk_status wk_quant_spec_default(wk_quant_spec* out) {
+  if (!out) return invalid("wk_quant_spec_default: null out");
+  *out = wk_quant_spec{-4, {-8, -9, -9, -9, -9}, {-5, -5, -4, -5, -4, -3}};
+  return WK_OK;
+}
+
+wk_status wk_set_quant(wk_handle* h, const wk_quant_spec* spec) {
+  if (!spec) return invalid("wk_set_quant: null spec");
+  wk::Int8Params p;
+  if (const char* why = wk::int8_params(*spec, &p)) return invalid(why);
+  if (!h) return invalid("wk_set_quant: null handle");
+  if (h->cfg.precision != WK_PREC_INT8 || !h->d_int8) return invalid("wk_set_quant: not a WK_PREC_INT8 handle with weights");
+  std::vector<int8_t> q(wk::kNumInt8Weights);
+  wk::quantize_int8_weights(h->h_w.data(), spec->e_w, q.data());
+  return on_device(h->cfg.device, [&]() -> wk_status {
+    // launches already queued (on any stream) still read the old bytes: drain them first
+    hipError_t e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "wk_set_quant: sync");
+    if ((e = hipMemcpy(h->d_int8, q.data(), q.size(), hipMemcpyHostToDevice)) != hipSuccess)
+      return hip_fail(e, "wk_set_quant: hipMemcpy(int8 weights)");
+    h->quant = *spec;
+    h->qp = p;
+    return WK_OK;
+  });
+}
+
+wk_status wk_get_quant(wk_handle* h, wk_quant_spec* out) {
+  if (!h || !out) return invalid("wk_get_quant: null argument");
+  if (h->cfg.precision != WK_PREC_INT8) return invalid("wk_get_quant: not a WK_PREC_INT8 handle");
+  *out = h->quant;
+  return WK_OK;
+}
+
+wk_status wk_quant_weights(const float* host_weights, const wk_quant_spec* spec, int8_t* out) {
+  if (!host_weights || !spec || !out) return invalid("wk_quant_weights: null argument");
+  for (int i = 0; i < 5; ++i)
+    if (spec->e_w[i] < -32 || spec->e_w[i] > 32) return invalid("wk_quant_weights: weight exponent outside [-32, 32]");
+  wk::quantize_int8_weights(host_weights, spec->e_w, out);
+  return WK_OK;
+}
+
+wk_status wk_calibrate_workspace_bytes(int64_t batch, size_t* bytes) {
+  if (!bytes) return invalid("wk_calibrate_workspace_bytes: null bytes");
+  *bytes = 0;
+  if (batch < 1) return invalid("wk_calibrate_workspace_bytes: batch < 1");
+  *bytes = wk::calibrate_workspace_bytes(batch);
+  return WK_OK;
+}
+
+wk_status wk_calibrate(wk_handle* h, const float* d_feats, int64_t batch, double percentile, int32_t pin_e_in,
+                       void* d_workspace, size_t workspace_bytes, wk_quant_spec* out, wk_calib_stats* stats_or_null,
+                       void* stream) {
+  if (!h) return invalid("wk_calibrate: null handle");
+  if (!h->d_weights) return invalid("wk_calibrate: handle created without weights");
+  if (!d_feats || !out || batch < 1) return invalid("wk_calibrate: null pointer or batch < 1");
+  if (!(percentile > 0.0)) return invalid("wk_calibrate: percentile must be > 0");
+  if (pin_e_in != WK_QUANT_CALIBRATE_INPUT && (pin_e_in < -32 || pin_e_in > 32))
+    return invalid("wk_calibrate: pinned input exponent outside [-32, 32]");
+  if (!d_workspace || ((uintptr_t)d_workspace & 255) || workspace_bytes < wk::calibrate_workspace_bytes(batch))
+    return invalid("wk_calibrate: workspace null, not 256-byte aligned or below wk_calibrate_workspace_bytes");
+  unsigned long long tot[wk::kCalibTotals];
+  const wk_status st = on_device(h->cfg.device, [&]() -> wk_status {
+    const hipStream_t s = (hipStream_t)stream;
+    hipError_t e = wk::launch_calibrate(h->d_weights, d_feats, batch, d_workspace, s);
+    if (e != hipSuccess) return hip_fail(e, "calibrate launch");
+    if ((e = hipMemcpyAsync(tot, d_workspace, sizeof(tot), hipMemcpyDeviceToHost, s)) != hipSuccess ||
+        (e = hipStreamSynchronize(s)) != hipSuccess)
+      return hip_fail(e, "wk_calibrate: read back");
+    return WK_OK;
+  });
+  if (st != WK_OK) return st;
+  static const int64_t per_clip[WK_QUANT_TENSORS] = {13 * 63, 32 * 63, 64 * 31, 128 * 15, 128, 64, 1};
+  int e_t[WK_QUANT_TENSORS];
+  for (int t = 0; t < WK_QUANT_TENSORS; ++t) {
+    const unsigned long long* c = tot + t * WK_QUANT_BINS;
+    const int64_t n = per_clip[t] * batch;
+    // the smallest bin whose cumulative count reaches k = ceil(percentile / 100 * n); >= 100: the maximum's bin
+    int64_t k = percentile >= 100.0 ? n : (int64_t)ceil(percentile / 100.0 * (double)n);
+    k = k < 1 ? 1 : (k > n ? n : k);
+    int64_t cum = 0;
+    int b = 0;
+    for (; b < WK_QUANT_BINS - 1; ++b)
+      if ((cum += (int64_t)c[b]) >= k) break;
+    e_t[t] = b - 24;
+    if (stats_or_null) {
+      for (int i = 0; i < WK_QUANT_BINS; ++i) stats_or_null->counts[t][i] = (int64_t)c[i];
+      const uint32_t mb = (uint32_t)tot[WK_QUANT_TENSORS * WK_QUANT_BINS + t];
+      memcpy(&stats_or_null->max_abs[t], &mb, 4);
+    }
+  }
+  if (stats_or_null) stats_or_null->n_clips = batch;
+  out->e_in = pin_e_in != WK_QUANT_CALIBRATE_INPUT ? pin_e_in : e_t[0];
+  for (int i = 0; i < 6; ++i) out->e_act[i] = e_t[1 + i];
+  static const int off[6] = {wk::kOffW1, wk::kOffW2, wk::kOffW3, wk::kOffF1, wk::kOffF2, wk::kNumWeights};
+  for (int i = 0; i < 5; ++i) {
+    float m = 0.0f;
+    for (int j = off[i]; j < off[i + 1]; ++j) m = fmaxf(m, fabsf(h->h_w[j]));
+    out->e_w[i] = hold_exp(m);
+  }
+  return WK_OK;
 }
 
 wk_status wk_synth_clips(uint32_t seed, int64_t first, int64_t count, int32_t n, float* d_out, void* stream) {

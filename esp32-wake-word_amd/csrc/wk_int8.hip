@@ -1,9 +1,14 @@
 // wk_int8.hip -- the xiaoa CNN in the device's int8 arithmetic (SURVEY 8(f)
 // item 3): esp-dl / esp-ppq power-of-2, symmetric, per-tensor int8
-// (ml_models/xiaoa.json:1-40), exponents from ml_models/xiaoa.info:3139-3150.
+// (ml_models/xiaoa.json:1-40).  The exponents are a handle's wk_quant_spec:
+// ml_models/xiaoa.info:3139-3150's by default -- shown below -- or any other
+// set (wk_set_quant, e.g. from wk_calibrate).  The kernels read the shifts s,
+// the GAP step d = e_conv3 - e_gap, 2^-e_in and 2^e_logit from the by-value
+// Int8Params of the launch; a compile-time instantiation of the default spec
+// measured no faster than run-time shifts, so there is none.
 //
 //   input    q = clamp(lroundf(x * 2^4))                      exp -4  (TensorBase::assign)
-//   conv k3  acc = sum q_x q_w (int32); q = clamp(rne(acc / 2^s)) s = e_x + e_w - e_out
+//   conv k3  acc = sum q_x q_w (int32); q = clamp(rne(acc / 2^s)) s = e_out - e_x - e_w
 //            ReLU fused, MaxPool(2) on int8
 //            conv1: -4 -8 -> -5 (s = 7); conv2: -5 -9 -> -5 (s = 9); conv3: -5 -9 -> -4 (s = 10)
 //   GAP      mean of 7, exp -4 -> -5: q = clamp(rne(2 s / 7))  (2s/7 never ties)
@@ -33,18 +38,42 @@ constexpr int kW0 = 3 * 13 * 32, kW3 = 3 * 32 * 64, kW6 = 3 * 64 * 128, kM23 = 1
 
 __device__ __forceinline__ int sat8(int v) { return v < -128 ? -128 : (v > 127 ? 127 : v); }
 
-// acc / 2^s rounded half to even (s >= 1), then saturated.
-__device__ __forceinline__ int rq(int acc, int s) {
-  int q = acc >> s;                       // floor
-  const int rem = acc - (q << s), half = 1 << (s - 1);
-  q += (rem > half || (rem == half && (q & 1))) ? 1 : 0;
+// GAP: sat8(rne(sum 2^d / 7)) of the 7 pooled steps' sum (>= 0).  d >= 0: floor((2 n + 7) / 14) with
+// n = sum << d, which never ties (7 is odd); d < 0: the divisor 7 * 2^-d is even, ties go to even.
+__device__ __forceinline__ int gap_q(int sum, int d) {
+  if (d >= 0) return sat8((2 * (sum << d) + 7) / 14);
+  const int dv = 7 << -d;
+  int q = sum / dv;
+  const int rem2 = 2 * (sum - q * dv);
+  q += (rem2 > dv || (rem2 == dv && (q & 1))) ? 1 : 0;
   return sat8(q);
 }
+
+// The constants of one launch.  acc / 2^s rounded half to even is (acc + 2^(s-1) - 1 + lsb(acc >> s)) >> s
+// (arithmetic shifts); the two per-layer terms are formed once (s = 0: both 0, saturate only).
+struct Consts {
+  int s[5], hm1[5], lsb[5], d;
+  float in_scale, out_scale;
+  __device__ __forceinline__ explicit Consts(const wk::Int8Params& p) : d(p.d), in_scale(p.in_scale), out_scale(p.out_scale) {
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+      s[i] = p.s[i];
+      hm1[i] = s[i] ? (1 << (s[i] - 1)) - 1 : 0;
+      lsb[i] = s[i] ? 1 : 0;
+    }
+  }
+  // layer i's accumulator -> int8 (conv1, conv2, conv3, classifier.0, classifier.2)
+  __device__ __forceinline__ int requant(int acc, int i) const {
+    return sat8((acc + hm1[i] + ((acc >> s[i]) & lsb[i])) >> s[i]);
+  }
+};
 
 // weights: int8 in logical layouts conv [k][ci][co], matmul [in][out] (quantize_int8_weights;
 // the esp-dl export stores the same values in its (N/16)WC16 order)
 __global__ __launch_bounds__(256) void wk_int8_cnn_kernel(const float* __restrict__ feats, int64_t batch,
-                                                          const int8_t* __restrict__ wq, float* __restrict__ logits) {
+                                                          const int8_t* __restrict__ wq, const wk::Int8Params p,
+                                                          float* __restrict__ logits) {
+  const Consts c(p);
   __shared__ int8_t w[kW0 + kW3 + kW6 + kM23 + kM24];
   __shared__ int x0[65][13];    // input, time-major, zero guard rows 0 and 64
   __shared__ int a1[33][32];    // pooled conv1, guards 0 and 32
@@ -61,8 +90,8 @@ __global__ __launch_bounds__(256) void wk_int8_cnn_kernel(const float* __restric
   for (int64_t b = blockIdx.x; b < batch; b += gridDim.x) {
     __syncthreads();
     for (int i = tid; i < 65 * 13; i += 256) {
-      const int t = i / 13, c = i - t * 13;
-      x0[t][c] = (t == 0 || t == 64) ? 0 : sat8((int)lroundf(feats[b * (13 * 63) + c * 63 + (t - 1)] * 16.0f));
+      const int t = i / 13, ci = i - t * 13;
+      x0[t][ci] = (t == 0 || t == 64) ? 0 : sat8((int)lroundf(feats[b * (13 * 63) + ci * 63 + (t - 1)] * c.in_scale));
     }
     for (int i = tid; i < 32; i += 256) a1[0][i] = a1[32][i] = 0;
     for (int i = tid; i < 64; i += 256) a2[0][i] = a2[16][i] = 0;
@@ -75,7 +104,7 @@ __global__ __launch_bounds__(256) void wk_int8_cnn_kernel(const float* __restric
         int acc = 0;
         for (int k = 0; k < 3; ++k)
           for (int ci = 0; ci < 13; ++ci) acc += x0[t + k][ci] * (int)W0[(k * 13 + ci) * 32 + co];
-        m = max(m, rq(acc, 7));
+        m = max(m, c.requant(acc, 0));
       }
       a1[tp + 1][co] = m;
     }
@@ -88,7 +117,7 @@ __global__ __launch_bounds__(256) void wk_int8_cnn_kernel(const float* __restric
         int acc = 0;
         for (int k = 0; k < 3; ++k)
           for (int ci = 0; ci < 32; ++ci) acc += a1[t + k][ci] * (int)W3[(k * 32 + ci) * 64 + co];
-        m = max(m, rq(acc, 9));
+        m = max(m, c.requant(acc, 1));
       }
       a2[tp + 1][co] = m;
     }
@@ -101,27 +130,27 @@ __global__ __launch_bounds__(256) void wk_int8_cnn_kernel(const float* __restric
         int acc = 0;
         for (int k = 0; k < 3; ++k)
           for (int ci = 0; ci < 64; ++ci) acc += a2[t + k][ci] * (int)W6[(k * 64 + ci) * 128 + co];
-        m = max(m, rq(acc, 10));
+        m = max(m, c.requant(acc, 2));
       }
       a3[tp][co] = m;
     }
     __syncthreads();
-    if (tid < 128) {   // GAP: exp -4 -> -5, q = rne(2 s / 7) = floor(2 s / 7 + 1/2) (no ties; s >= 0)
+    if (tid < 128) {   // GAP (default spec: exp -4 -> -5, q = rne(2 s / 7))
       int s = 0;
       for (int t = 0; t < 7; ++t) s += a3[t][tid];
-      g[tid] = sat8((4 * s + 7) / 14);
+      g[tid] = gap_q(s, c.d);
     }
     __syncthreads();
     if (tid < 64) {
       int acc = 0;
-      for (int c = 0; c < 128; ++c) acc += g[c] * (int)M23[c * 64 + tid];
-      hid[tid] = max(0, rq(acc, 10));
+      for (int k = 0; k < 128; ++k) acc += g[k] * (int)M23[k * 64 + tid];
+      hid[tid] = max(0, c.requant(acc, 3));
     }
     __syncthreads();
     if (tid < 64) {
       int v = hid[tid] * (int)M24[tid];
       for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-      if (tid == 0) logits[b] = (float)rq(v, 10) * 0.125f;
+      if (tid == 0) logits[b] = (float)c.requant(v, 4) * c.out_scale;
     }
   }
 }
@@ -159,8 +188,9 @@ __device__ __forceinline__ unsigned pack4(int a, int b, int c, int d) {
 }
 
 __global__ __launch_bounds__(64 * kQW) void wk_int8_mfma_kernel(const float* __restrict__ feats, int64_t batch,
-                                                                 const int8_t* __restrict__ wq,
+                                                                 const int8_t* __restrict__ wq, const wk::Int8Params p,
                                                                  float* __restrict__ logits) {
+  const Consts cq(p);
   __shared__ int8_t w[kW0 + kW3 + kW6 + kM23 + kM24];
   __shared__ __attribute__((aligned(16))) int8_t img[kQW][kX0 + kA1 + kA2 + 128];
   __shared__ i32x4 fimg[10][64];
@@ -208,18 +238,18 @@ __global__ __launch_bounds__(64 * kQW) void wk_int8_mfma_kernel(const float* __r
   const int m24 = M24[lane];
   const int64_t wstride = (int64_t)gridDim.x * kQW;
   for (int64_t b = (int64_t)blockIdx.x * kQW + wv; b < batch; b += wstride) {
-    // input: x0[t + 1][c] = sat8(lround(16 x[c][t])), t < 63, c < 13
+    // input: x0[t + 1][c] = sat8(lround(x[c][t] 2^-e_in)), t < 63, c < 13
     const float* f = feats + b * (13 * 63);
 #pragma unroll
     for (int m = 0; m < 13; ++m) {
       const int e = lane + 64 * m;   // < 832; 819 values
       if (e < 13 * 63) {
         const int c = e / 63, t = e - 63 * c;
-        x0[(t + 1) * 16 + c] = (int8_t)sat8((int)lroundf(f[e] * 16.0f));
+        x0[(t + 1) * 16 + c] = (int8_t)sat8((int)lroundf(f[e] * cq.in_scale));
       }
     }
     wk::wave_lds_sync();
-    // conv1 (s = 7): 4 column tiles of t, K = 3 x 16 (lane group 3: zeros)
+    // conv1 (default s = 7): 4 column tiles of t, K = 3 x 16 (lane group 3: zeros)
 #pragma unroll
     for (int tt = 0; tt < 4; ++tt) {
       const int t = 16 * tt + li;
@@ -231,7 +261,7 @@ __global__ __launch_bounds__(64 * kQW) void wk_int8_mfma_kernel(const float* __r
         int q[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          const int v = rq(acc[i], 7);
+          const int v = cq.requant(acc[i], 0);
           q[i] = max(0, max(v, q_even(v)));
         }
         const int tp = t >> 1;
@@ -239,7 +269,7 @@ __global__ __launch_bounds__(64 * kQW) void wk_int8_mfma_kernel(const float* __r
       }
     }
     wk::wave_lds_sync();
-    // conv2 (s = 9): 2 column tiles, K = 2 steps over (k, ci < 32)
+    // conv2 (default s = 9): 2 column tiles, K = 2 steps over (k, ci < 32)
 #pragma unroll
     for (int tt = 0; tt < 2; ++tt) {
       const int t = 16 * tt + li;
@@ -259,14 +289,14 @@ __global__ __launch_bounds__(64 * kQW) void wk_int8_mfma_kernel(const float* __r
         int q[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          const int v = rq(acc[ct][i], 9);
+          const int v = cq.requant(acc[ct][i], 1);
           q[i] = max(0, max(v, q_even(v)));
         }
         if (!(li & 1) && tp < 15) *reinterpret_cast<unsigned*>(a2 + (tp + 1) * 64 + 16 * ct + 4 * lg) = pack4(q[0], q[1], q[2], q[3]);
       }
     }
     wk::wave_lds_sync();
-    // conv3 (s = 10): one column tile (t < 14 used), K = 3 steps, one per tap;
+    // conv3 (default s = 10): one column tile (t < 14 used), K = 3 steps, one per tap;
     // pool, then GAP over the 7 pooled steps: a 16-lane row sum of the even lanes
     {
       i32x4 acc[8] = {};
@@ -282,24 +312,24 @@ __global__ __launch_bounds__(64 * kQW) void wk_int8_mfma_kernel(const float* __r
         int gs[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          const int v = rq(acc[ct][i], 10);
+          const int v = cq.requant(acc[ct][i], 2);
           const int p = max(0, max(v, q_even(v)));
           const int sum = row16_sum_i(live ? p : 0);
-          gs[i] = sat8((4 * sum + 7) / 14);   // GAP: exp -4 -> -5, rne(2 s / 7)
+          gs[i] = gap_q(sum, cq.d);   // default spec: exp -4 -> -5, rne(2 s / 7)
         }
         if (li == 0) *reinterpret_cast<unsigned*>(gq + 16 * ct + 4 * lg) = pack4(gs[0], gs[1], gs[2], gs[3]);
       }
     }
     wk::wave_lds_sync();
-    // MatMul 128 -> 64 (s = 10) + ReLU: lane o, 32 dot4 over the broadcast g bytes
+    // MatMul 128 -> 64 (default s = 10) + ReLU: lane o, 32 dot4 over the broadcast g bytes
     int acc = 0;
 #pragma unroll
     for (int j = 0; j < 32; ++j) acc = __builtin_amdgcn_sdot4(*reinterpret_cast<const int*>(gq + 4 * j), m23t[j][lane], acc, false);
-    const int hid = max(0, rq(acc, 10));
-    int v = hid * m24;   // MatMul 64 -> 1 (s = 10)
+    const int hid = max(0, cq.requant(acc, 3));
+    int v = hid * m24;   // MatMul 64 -> 1 (default s = 10)
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    if (lane == 0) logits[b] = (float)rq(v, 10) * 0.125f;
+    if (lane == 0) logits[b] = (float)cq.requant(v, 4) * cq.out_scale;
     wk::wave_lds_sync();   // this clip's images are read before the next clip's input overwrites x0
   }
 }
@@ -308,43 +338,63 @@ __global__ __launch_bounds__(64 * kQW) void wk_int8_mfma_kernel(const float* __r
 
 namespace wk {
 
-hipError_t launch_int8_cnn(const float* feats, int64_t batch, const int8_t* wq, float* logits, int grid_cap,
-                           hipStream_t stream) {
+const char* int8_params(const wk_quant_spec& q, Int8Params* p) {
+  const int32_t* all = &q.e_in;   // e_in, e_w[5], e_act[6]: twelve int32_t in a row
+  static_assert(sizeof(wk_quant_spec) == 12 * sizeof(int32_t), "wk_quant_spec layout");
+  for (int i = 0; i < 12; ++i)
+    if (all[i] < -32 || all[i] > 32) return "quant spec: exponent outside [-32, 32]";
+  const int e_x[5] = {q.e_in, q.e_act[0], q.e_act[1], q.e_act[3], q.e_act[4]};
+  const int e_out[5] = {q.e_act[0], q.e_act[1], q.e_act[2], q.e_act[4], q.e_act[5]};
+  for (int i = 0; i < 5; ++i) {
+    p->s[i] = e_out[i] - e_x[i] - q.e_w[i];
+    if (p->s[i] < 0 || p->s[i] > 24) return "quant spec: a requantisation shift e_out - e_x - e_w is outside [0, 24]";
+  }
+  p->d = q.e_act[2] - q.e_act[3];
+  if (p->d < -4 || p->d > 4) return "quant spec: e_act[conv3] - e_act[gap] is outside [-4, 4]";
+  p->in_scale = ldexpf(1.0f, -q.e_in);
+  p->out_scale = ldexpf(1.0f, q.e_act[5]);
+  return nullptr;
+}
+
+hipError_t launch_int8_cnn(const float* feats, int64_t batch, const int8_t* wq, const Int8Params& p, float* logits,
+                           int grid_cap, hipStream_t stream) {
   if (batch == 0) return hipSuccess;
   static const bool checking = getenv("WAKEWORD_INT8_VALU") != nullptr;   // the one-block-per-clip VALU kernel (A/B, checks)
   if (checking) {
     const int grid = (int)(batch < grid_cap ? batch : grid_cap);
-    hipLaunchKernelGGL(wk_int8_cnn_kernel, dim3(grid), dim3(256), 0, stream, feats, batch, wq, logits);
+    hipLaunchKernelGGL(wk_int8_cnn_kernel, dim3(grid), dim3(256), 0, stream, feats, batch, wq, p, logits);
   } else {
     const int64_t blocks = (batch + kQW - 1) / kQW;
     const int grid = (int)(blocks < grid_cap ? blocks : grid_cap);
-    hipLaunchKernelGGL(wk_int8_mfma_kernel, dim3(grid), dim3(64 * kQW), 0, stream, feats, batch, wq, logits);
+    hipLaunchKernelGGL(wk_int8_mfma_kernel, dim3(grid), dim3(64 * kQW), 0, stream, feats, batch, wq, p, logits);
   }
   return hipGetLastError();
 }
 
 // Quantise the fp32 state dict blob (WK_NUM_WEIGHTS layout) to the int8 export:
-// rne(w * 2^-e) with the per-tensor weight exponents of xiaoa.info
-// (conv -8, -9, -9; matmul -9, -9), re-laid out conv [k][ci][co], matmul [in][out].
-void quantize_int8_weights(const float* w, int8_t* q) {
+// sat8(rne(w * 2^-e)) with the per-tensor weight exponents e_w[5] (xiaoa.info:
+// conv -8, -9, -9; matmul -9, -9), re-laid out conv [k][ci][co], matmul [in][out].
+void quantize_int8_weights(const float* w, const int32_t* e_w, int8_t* q) {
   auto qz = [](float v, int e) {
     const float s = ldexpf(v, -e);
+    if (!(s > -129.0f)) return (int8_t)-128;   // (also NaN)
+    if (s > 128.0f) return (int8_t)127;
     const long r = lrintf(s);   // round half to even (default rounding mode)
     return (int8_t)(r < -128 ? -128 : (r > 127 ? 127 : r));
   };
   int8_t* o = q;
   for (int k = 0; k < 3; ++k)
     for (int ci = 0; ci < 13; ++ci)
-      for (int co = 0; co < 32; ++co) *o++ = qz(w[kOffW1 + (co * 13 + ci) * 3 + k], -8);
+      for (int co = 0; co < 32; ++co) *o++ = qz(w[kOffW1 + (co * 13 + ci) * 3 + k], e_w[0]);
   for (int k = 0; k < 3; ++k)
     for (int ci = 0; ci < 32; ++ci)
-      for (int co = 0; co < 64; ++co) *o++ = qz(w[kOffW2 + (co * 32 + ci) * 3 + k], -9);
+      for (int co = 0; co < 64; ++co) *o++ = qz(w[kOffW2 + (co * 32 + ci) * 3 + k], e_w[1]);
   for (int k = 0; k < 3; ++k)
     for (int ci = 0; ci < 64; ++ci)
-      for (int co = 0; co < 128; ++co) *o++ = qz(w[kOffW3 + (co * 64 + ci) * 3 + k], -9);
+      for (int co = 0; co < 128; ++co) *o++ = qz(w[kOffW3 + (co * 64 + ci) * 3 + k], e_w[2]);
   for (int c = 0; c < 128; ++c)
-    for (int oo = 0; oo < 64; ++oo) *o++ = qz(w[kOffF1 + oo * 128 + c], -9);
-  for (int c = 0; c < 64; ++c) *o++ = qz(w[kOffF2 + c], -9);
+    for (int oo = 0; oo < 64; ++oo) *o++ = qz(w[kOffF1 + oo * 128 + c], e_w[3]);
+  for (int c = 0; c < 64; ++c) *o++ = qz(w[kOffF2 + c], e_w[4]);
 }
 
 }  // namespace wk

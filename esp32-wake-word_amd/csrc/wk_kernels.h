@@ -72,9 +72,33 @@ hipError_t launch_cnn_fused(const float* feats, int64_t batch, const float* w, c
 
 // int8 CNN in the device's esp-dl arithmetic (wk_int8.hip); feats [B][13][63] fp32.
 constexpr int kNumInt8Weights = 3 * 13 * 32 + 3 * 32 * 64 + 3 * 64 * 128 + 128 * 64 + 64;
-hipError_t launch_int8_cnn(const float* feats, int64_t batch, const int8_t* wq, float* logits, int grid_cap,
-                           hipStream_t stream);
-void quantize_int8_weights(const float* w, int8_t* q);
+// Int8Params: what the kernels derive from a wk_quant_spec, passed by value.  s = the requantisation shifts of
+// conv1, conv2, conv3, classifier.0, classifier.2; d = GAP's e_conv3 - e_gap; the scales are 2^-e_in and 2^e_logit.
+struct Int8Params {
+  int s[5];
+  int d;
+  float in_scale, out_scale;
+};
+// WK_ERR_INVALID_ARG text, or nullptr when `spec` is runnable (wk_set_quant's limits); fills *p.
+const char* int8_params(const wk_quant_spec& spec, Int8Params* p);
+hipError_t launch_int8_cnn(const float* feats, int64_t batch, const int8_t* wq, const Int8Params& p, float* logits,
+                           int grid_cap, hipStream_t stream);
+void quantize_int8_weights(const float* w, const int32_t* e_w, int8_t* q);
+
+// Calibration (wk_quant.hip).  Workspace: the 64-bit totals ([7][32] counts, then the 7 maxima as bit
+// patterns of |x|), fragment-major forward weights, then one slot of kCalibSlot 32-bit words per workgroup
+// (7 x 32 counts, 7 maxima).  Workgroup g walks clips g, g + grid, ...; grid = min(batch, kCalibGridCap).
+constexpr int kCalibTotals = WK_QUANT_TENSORS * WK_QUANT_BINS + WK_QUANT_TENSORS;
+constexpr int kCalibSlot = WK_QUANT_TENSORS * WK_QUANT_BINS + 8;
+constexpr int kCalibGridCap = 512;
+constexpr int kCalibPacked = (2 * 12 + 4 * 24 + 8 * 48) * 64;   // floats
+constexpr size_t kCalibTotalsBytes = (kCalibTotals * 8 + 255) & ~(size_t)255;
+inline size_t calibrate_workspace_bytes(int64_t batch) {
+  const int64_t grid = batch < kCalibGridCap ? batch : kCalibGridCap;
+  return kCalibTotalsBytes + sizeof(float) * kCalibPacked + sizeof(uint32_t) * kCalibSlot * (size_t)grid;
+}
+// Queues the pack, count and sum kernels; the totals are at the start of the workspace afterwards.
+hipError_t launch_calibrate(const float* w, const float* feats, int64_t batch, void* workspace, hipStream_t stream);
 
 // Misc (wk_misc.hip).
 hipError_t launch_synth(uint32_t seed, int64_t first, int64_t count, int n, float* out, hipStream_t stream);

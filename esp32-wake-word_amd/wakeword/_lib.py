@@ -33,7 +33,12 @@ EXPORTS = ("wk_create", "wk_destroy", "wk_mfcc", "wk_cnn", "wk_forward", "wk_syn
            "wk_check_device_errors", "wk_ctc_frame_argmax", "wk_record_front", "wk_quantize_frames",
            "wk_ctc_profile", "wk_ctc_stage_times", "wk_ctc_transcribe", "wk_esp_mfcc_create", "wk_esp_mfcc_run",
            "wk_esp_mfcc_destroy", "wk_scan", "wk_scan_workspace_bytes", "wk_trainer_create", "wk_trainer_destroy",
-           "wk_trainer_grad", "wk_trainer_step", "wk_trainer_weights")
+           "wk_trainer_grad", "wk_trainer_step", "wk_trainer_weights", "wk_quant_spec_default", "wk_set_quant",
+           "wk_get_quant", "wk_quant_weights", "wk_calibrate_workspace_bytes", "wk_calibrate")
+WK_NUM_INT8_WEIGHTS = 3 * 13 * 32 + 3 * 32 * 64 + 3 * 64 * 128 + 128 * 64 + 64
+WK_QUANT_TENSORS = 7
+WK_QUANT_BINS = 32
+WK_QUANT_CALIBRATE_INPUT = -2 ** 31
 
 
 class WkConfig(C.Structure):
@@ -49,6 +54,15 @@ class WkCtcConfig(C.Structure):
 class WkAdamW(C.Structure):
     _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
                 ("weight_decay", C.c_float)]
+
+
+class WkQuantSpec(C.Structure):
+    _fields_ = [("e_in", C.c_int32), ("e_w", C.c_int32 * 5), ("e_act", C.c_int32 * 6)]
+
+
+class WkCalibStats(C.Structure):
+    _fields_ = [("n_clips", C.c_int64), ("counts", (C.c_int64 * WK_QUANT_BINS) * WK_QUANT_TENSORS),
+                ("max_abs", C.c_float * WK_QUANT_TENSORS)]
 
 
 class WkWavInfo(C.Structure):
@@ -117,6 +131,14 @@ def _declare(L):
         L.wk_trainer_grad.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp]
         L.wk_trainer_step.argtypes = [vp, C.POINTER(WkAdamW), vp, vp]
         L.wk_trainer_weights.argtypes = [vp, vp, vp]
+    if hasattr(L, "wk_calibrate"):   # (absent from older libraries loaded for A/B timing)
+        L.wk_quant_spec_default.argtypes = [C.POINTER(WkQuantSpec)]
+        L.wk_set_quant.argtypes = [vp, C.POINTER(WkQuantSpec)]
+        L.wk_get_quant.argtypes = [vp, C.POINTER(WkQuantSpec)]
+        L.wk_quant_weights.argtypes = [vp, C.POINTER(WkQuantSpec), vp]
+        L.wk_calibrate_workspace_bytes.argtypes = [i64, C.POINTER(C.c_size_t)]
+        L.wk_calibrate.argtypes = [vp, vp, i64, C.c_double, i32, vp, C.c_size_t, C.POINTER(WkQuantSpec),
+                                   C.POINTER(WkCalibStats), vp]
     for name in ("wk_create", "wk_destroy", "wk_mfcc", "wk_cnn", "wk_forward", "wk_synth_clips", "wk_normalize",
                  "wk_stream_create", "wk_stream_destroy", "wk_stream_reset", "wk_stream_push", "wk_ctc_create",
                  "wk_ctc_destroy", "wk_ctc_features", "wk_ctc_forward", "wk_wav_read", "wk_wav_load_batch",
@@ -124,7 +146,8 @@ def _declare(L):
                  "wk_quantize_frames", "wk_ctc_profile", "wk_ctc_stage_times", "wk_ctc_transcribe",
                  "wk_esp_mfcc_create", "wk_esp_mfcc_run", "wk_esp_mfcc_destroy", "wk_scan",
                  "wk_scan_workspace_bytes", "wk_trainer_create", "wk_trainer_destroy", "wk_trainer_grad",
-                 "wk_trainer_step", "wk_trainer_weights"):
+                 "wk_trainer_step", "wk_trainer_weights", "wk_quant_spec_default", "wk_set_quant", "wk_get_quant",
+                 "wk_quant_weights", "wk_calibrate_workspace_bytes", "wk_calibrate"):
         if hasattr(L, name):
             getattr(L, name).restype = i32
 

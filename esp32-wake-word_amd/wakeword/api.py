@@ -170,13 +170,30 @@ class KWSModel:
     input_names = ("input.1",)
     output_names = ("22",)
 
-    def __init__(self, state_dict: Dict[str, np.ndarray], device: int = 0, precision: str = "fp32"):
+    def __init__(self, state_dict: Dict[str, np.ndarray], device: int = 0, precision: str = "fp32", quant=None):
+        """quant (precision 'int8' only): the wakeword.quant.QuantSpec the int8
+        network runs at; None = ml_models/xiaoa.info's exponents."""
         self._sd = {k: np.ascontiguousarray(state_dict[k], np.float32) for k in STATE_KEYS}
         self.device = device
         self.precision = precision
+        if quant is not None and precision != "int8":
+            raise ValueError("quant applies to precision='int8' only")
         self._h = _Handle(_lib.WK_MODE_TORCHAUDIO_CMVN, pack_weights(self._sd), device,
                           {"fp32": _lib.WK_PREC_FP32, "bf16": _lib.WK_PREC_BF16, "int8": _lib.WK_PREC_INT8,
                            "bf16x3": _lib.WK_PREC_BF16X3}[precision])
+        if quant is not None:
+            c = quant._to_c()
+            check(lib().wk_set_quant(self._h.h, C.byref(c)), "wk_set_quant")
+
+    @property
+    def quant(self):
+        """The QuantSpec in force (int8 models; None otherwise)."""
+        if self.precision != "int8":
+            return None
+        from .quant import QuantSpec
+        c = _lib.WkQuantSpec()
+        check(lib().wk_get_quant(self._h.h, C.byref(c)), "wk_get_quant")
+        return QuantSpec._from_c(c)
 
     # -- nn.Module-like surface ------------------------------------------------
     def state_dict(self) -> Dict[str, np.ndarray]:
@@ -275,10 +292,10 @@ class KWSModel:
         check(lib().wk_check_device_errors(self._h.h, C.byref(flags)), "wk_check_device_errors")
 
 
-def load_onnx(path: str, device: int = 0, precision: str = "fp32") -> KWSModel:
+def load_onnx(path: str, device: int = 0, precision: str = "fp32", quant=None) -> KWSModel:
     """Load ``xiaoa.onnx`` (ml_models/xiaoa.onnx) into a device-resident KWSModel."""
     inits, inputs, outputs = read_onnx(path)
-    m = KWSModel(xiaoa_state_dict(inits), device=device, precision=precision)
+    m = KWSModel(xiaoa_state_dict(inits), device=device, precision=precision, quant=quant)
     if inputs:
         m.input_names = tuple(inputs)
     if outputs:

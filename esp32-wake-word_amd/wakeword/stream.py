@@ -220,6 +220,12 @@ class DeviceDetector:
 
     def __init__(self, model, threshold_pct: float = 80.0, refractory_s: float = 5.0, frame_s: float = 0.02,
                  cleared_inference: bool = True):
+        # wk_device_cmvn hands over the firmware's integer frames, which the int8
+        # network takes at x16: only an input exponent of -4 reads them as the firmware does
+        spec = getattr(model, "quant", None)
+        if spec is not None and spec.e_in != -4:
+            raise ValueError(f"DeviceDetector needs an int8 model with input exponent -4 (the firmware's x16), "
+                             f"got {spec.e_in}")
         self._model = model
         self.loop = FrameDecisionLoop(threshold_pct, int(round(refractory_s / frame_s)), cleared_inference)
         self._tail = None          # the last <= 62 frames of earlier pushes

@@ -135,8 +135,19 @@ class Trainer:
         blob = self.weights().cpu().numpy()
         return {k: v.copy() for k, v in _split(blob).items()}
 
-    def to_model(self, precision: str = "fp32") -> KWSModel:
-        return KWSModel(self.state_dict(), device=self.device, precision=precision)
+    def to_model(self, precision: str = "fp32", calib=None, percentile: float = 99.9,
+                 pin_input_exp: Optional[int] = -4) -> KWSModel:
+        """A KWSModel of the current weights.  precision 'int8' with `calib`
+        ((B, 13, 63) features): the int8 network at exponents calibrated on
+        them (wakeword.quant.calibrate); without, at xiaoa.info's."""
+        sd = self.state_dict()
+        if calib is None:
+            return KWSModel(sd, device=self.device, precision=precision)
+        if precision != "int8":
+            raise ValueError("calib applies to precision='int8' only")
+        from .quant import calibrate
+        spec = calibrate(sd, calib, percentile=percentile, pin_input_exp=pin_input_exp, device=self.device)
+        return KWSModel(sd, device=self.device, precision="int8", quant=spec)
 
 
 def train_model(train_loader: Iterable, test_loader: Iterable, num_epochs: int, learning_rate: float = 0.001,

@@ -50,7 +50,8 @@ typedef enum { WK_DTYPE_F32 = 0, WK_DTYPE_I16 = 1, WK_DTYPE_I8 = 2 } wk_dtype;  
  * config 4), fp32 front-end/classifier.  INT8 = the device's esp-dl int8
  * network (power-of-2 per-tensor exponents of ml_models/xiaoa.info,
  * round-half-even requant; reproduces the xiaoa.info known-answer test
- * exactly): a device-faithful checking mode, run unfused after the fp32
+ * exactly; wk_set_quant runs it at another model's exponents, wk_calibrate
+ * finds them): a device-faithful mode, run unfused after the fp32
  * front-end.  BF16X3 = fp32-grade convolutions on bf16 MFMA: activations and
  * weights split into bf16 hi + lo parts, products hi*hi + hi*lo + lo*hi
  * accumulated in fp32 (relative product error ~2^-16); same logit tolerance
@@ -363,6 +364,66 @@ wk_status wk_trainer_step(wk_trainer* t, const wk_adamw* opt, const float* d_gra
 
 /* Current weights, blob order, device to device, stream-ordered. */
 wk_status wk_trainer_weights(wk_trainer* t, float* d_out, void* stream);
+
+/* ---- Post-training int8 quantisation (ml_models/main.py:71-129, quantize_model_esp) ----
+ * The int8 network's power-of-2, symmetric, per-tensor exponents: a tensor
+ * holds q * 2^e with q in [-128, 127].  e_w follows the state-dict order of
+ * WK_NUM_WEIGHTS; e_act is conv1, conv2, conv3 output (a pool output shares its
+ * conv's exponent), GAP, classifier.0 output, logit.  A convolution or matmul
+ * requantises its int32 sum by s = e_out - e_x - e_w bits (round half to even,
+ * then saturate; s = 0 saturates only); GAP computes rne(sum * 2^d / 7) with
+ * d = e_act[2] - e_act[3]. */
+typedef struct {
+  int32_t e_in;
+  int32_t e_w[5];
+  int32_t e_act[6];
+} wk_quant_spec;
+#define WK_QUANT_TENSORS 7   /* observed tensors: input, then e_act's six */
+#define WK_QUANT_BINS 32     /* exponents -24 .. 7 */
+
+/* ml_models/xiaoa.info:3139-3150: -4; -8 -9 -9 -9 -9; -5 -5 -4 -5 -4 -3. */
+wk_status wk_quant_spec_default(wk_quant_spec* out);
+/* WK_PREC_INT8 handles only: re-quantise the handle's fp32 weights as
+ * sat8(rne(w * 2^-e_w)) and run every later int8 launch of the handle (wk_cnn,
+ * wk_forward, wk_scan, wk_stream_push) at `spec`.  Blocks until the handle's
+ * device is idle, so it is safe between calls on any stream; launches already
+ * queued keep the spec they were issued with.  WK_ERR_INVALID_ARG, before any
+ * device work, if the handle is not int8, an exponent is outside [-32, 32], a
+ * shift s is outside [0, 24] or d is outside [-4, 4].  A handle that never
+ * calls it runs the default spec. */
+wk_status wk_set_quant(wk_handle* h, const wk_quant_spec* spec);
+wk_status wk_get_quant(wk_handle* h, wk_quant_spec* out);
+/* Host only: the int8 export of a WK_NUM_WEIGHTS blob at spec->e_w (only e_w
+ * is read, each in [-32, 32]), WK_NUM_WEIGHTS values in the logical layouts
+ * conv [k][ci][co], matmul [in][out]. */
+wk_status wk_quant_weights(const float* host_weights, const wk_quant_spec* spec, int8_t* out);
+
+/* Calibration: one fp32 forward of the CNN (direct-form convolutions on fp32
+ * MFMA, the handle's fp32 weights; any precision) over d_feats [batch][13][63],
+ * observing per clip the input (819 values), the conv1 / conv2 / conv3 outputs
+ * after ReLU and before the pool (2016, 1984, 1920), GAP (128), classifier.0
+ * after ReLU (64) and the logit (1).  |x| is counted in the bin of the smallest
+ * exponent that holds it, b = min{e : |x| <= 127 * 2^e}, clamped to [-24, 7]
+ * (zeros in the lowest bin).  Per tensor, the exponent is the smallest bin
+ * whose cumulative count reaches ceil(percentile / 100 * N); percentile >= 100
+ * gives the bin of the maximum.  pin_e_in fixes e_in (the firmware feeds x16:
+ * -4) unless it is WK_QUANT_CALIBRATE_INPUT; weight exponents are
+ * ceil(log2(max|w| / 127)) per tensor.  Counts are integers summed in a fixed
+ * way (no floating-point or global atomics): two calls give the same result.
+ * The call allocates nothing and synchronises `stream` once, to read the
+ * counters back.  The workspace is device memory of at least
+ * wk_calibrate_workspace_bytes(batch) bytes, 256-byte aligned.  The result is
+ * not checked against wk_set_quant's shift limits: wk_set_quant does that. */
+typedef struct {
+  int64_t n_clips;
+  int64_t counts[WK_QUANT_TENSORS][WK_QUANT_BINS];
+  float max_abs[WK_QUANT_TENSORS];
+} wk_calib_stats;
+#define WK_QUANT_CALIBRATE_INPUT INT32_MIN
+wk_status wk_calibrate_workspace_bytes(int64_t batch, size_t* bytes);
+wk_status wk_calibrate(wk_handle* h, const float* d_feats, int64_t batch, double percentile, int32_t pin_e_in,
+                       void* d_workspace, size_t workspace_bytes, wk_quant_spec* out, wk_calib_stats* stats_or_null,
+                       void* stream);
 
 /* Human-readable text for a status / the last HIP error seen by this thread. */
 const char* wk_status_string(wk_status s);
