@@ -11,6 +11,7 @@
 
 #include "wakeword.h"
 #include "wk_kernels.h"
+#include "wk_quant_rule.h"
 
 struct wk_handle {
   wk_config cfg;
@@ -459,21 +460,6 @@ wk_status wk_scan(wk_handle* h, const void* d_audio, int32_t dtype, int64_t n_re
 // ---------------------------------------------------------------------------
 // Post-training int8 quantisation: the spec, and calibration's host step.
 // ---------------------------------------------------------------------------
-namespace {
-
-// b(a) = min{e : a <= 127 * 2^e} from the float's bits, clamped to [-24, 7]: 127 * 2^e = 1.984375 * 2^(e + 6),
-// mantissa field 0x7E0000, so with exponent field E it is E - 6 up to that mantissa and E - 5 above it.
-// (wk_quant.hip's kernel bins with the same rule.)
-int hold_exp(float a) {
-  uint32_t u;
-  memcpy(&u, &a, 4);
-  u &= 0x7FFFFFFFu;
-  const int b = (int)(u >> 23) - 127 - ((u & 0x7FFFFFu) <= 0x7E0000u ? 6 : 5);
-  return u == 0 || b < -24 ? -24 : (b > 7 ? 7 : b);
-}
-
-}  // namespace
-
 wk_status wk_quant_spec_default(wk_quant_spec* out) {
   if (!out) return invalid("wk_quant_spec_default: null out");
   *out = wk_quant_spec{-4, {-8, -9, -9, -9, -9}, {-5, -5, -4, -5, -4, -3}};
@@ -545,11 +531,10 @@ wk_status wk_calibrate(wk_handle* h, const float* d_feats, int64_t batch, double
     return WK_OK;
   });
   if (st != WK_OK) return st;
-  static const int64_t per_clip[WK_QUANT_TENSORS] = {13 * 63, 32 * 63, 64 * 31, 128 * 15, 128, 64, 1};
   int e_t[WK_QUANT_TENSORS];
   for (int t = 0; t < WK_QUANT_TENSORS; ++t) {
     const unsigned long long* c = tot + t * WK_QUANT_BINS;
-    const int64_t n = per_clip[t] * batch;
+    const int64_t n = wk::kCalibPerClip[t] * batch;
     // the smallest bin whose cumulative count reaches k = ceil(percentile / 100 * n); >= 100: the maximum's bin
     int64_t k = percentile >= 100.0 ? n : (int64_t)ceil(percentile / 100.0 * (double)n);
     k = k < 1 ? 1 : (k > n ? n : k);
@@ -571,7 +556,7 @@ wk_status wk_calibrate(wk_handle* h, const float* d_feats, int64_t batch, double
   for (int i = 0; i < 5; ++i) {
     float m = 0.0f;
     for (int j = off[i]; j < off[i + 1]; ++j) m = fmaxf(m, fabsf(h->h_w[j]));
-    out->e_w[i] = hold_exp(m);
+    out->e_w[i] = wk::hold_exp(m);
   }
   return WK_OK;
 }

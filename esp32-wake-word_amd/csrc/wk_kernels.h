@@ -91,14 +91,19 @@ void quantize_int8_weights(const float* w, const int32_t* e_w, int8_t* q);
 constexpr int kCalibTotals = WK_QUANT_TENSORS * WK_QUANT_BINS + WK_QUANT_TENSORS;
 constexpr int kCalibSlot = WK_QUANT_TENSORS * WK_QUANT_BINS + 8;
 constexpr int kCalibGridCap = 512;
-constexpr int kCalibPacked = (2 * 12 + 4 * 24 + 8 * 48) * 64;   // floats
 constexpr size_t kCalibTotalsBytes = (kCalibTotals * 8 + 255) & ~(size_t)255;
-inline size_t calibrate_workspace_bytes(int64_t batch) {
-  const int64_t grid = batch < kCalibGridCap ? batch : kCalibGridCap;
-  return kCalibTotalsBytes + sizeof(float) * kCalibPacked + sizeof(uint32_t) * kCalibSlot * (size_t)grid;
-}
+size_t calibrate_workspace_bytes(int64_t batch);
 // Queues the pack, count and sum kernels; the totals are at the start of the workspace afterwards.
 hipError_t launch_calibrate(const float* w, const float* feats, int64_t batch, void* workspace, hipStream_t stream);
+// Time steps of the input and after each of the three pools (the widths the direct-form tiles of wk_direct_dev.h
+// are cut to), and with them the values per clip of the seven tensors calibration observes.
+constexpr int kConvSteps[4] = {63, 31, 15, 7};
+constexpr int64_t kCalibPerClip[WK_QUANT_TENSORS] = {13 * kConvSteps[0], 32 * kConvSteps[0], 64 * kConvSteps[1],
+                                                     128 * kConvSteps[2], 128, 64, 1};
+
+// Fragment-major weights of the direct-form convolutions (wk_train.hip; layout in wk_direct_dev.h): the first
+// `count` floats of pk, kDirectFwdPacked (forward order only) or the trainer's forward + transposed.
+hipError_t launch_pack_direct(const float* w, float* pk, int count, hipStream_t stream);
 
 // Misc (wk_misc.hip).
 hipError_t launch_synth(uint32_t seed, int64_t first, int64_t count, int n, float* out, hipStream_t stream);

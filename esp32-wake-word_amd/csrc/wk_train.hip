@@ -24,11 +24,11 @@
 // calls give the same bits).  HBM traffic per clip is the 3276 bytes of
 // features, 4 of label and 4 of logit; the workspace costs 160 KB per
 // workgroup per call, not per clip.
-// A operands come from a fragment-major copy of the weights that
-// wk_train_pack_kernel rebuilds at the start of every call (the weights change
-// every step): forward order and transposed (data-gradient) order.
-#include "wk_cnn_dev.h"
-#include "wk_kernels.h"
+// The forward pass is wk_direct_dev.h's (calibration runs the same one); its A
+// operands and the data pass's come from a fragment-major copy of the weights
+// that wk_pack_direct_kernel rebuilds at the start of every call (the weights
+// change every step): forward order and transposed (data-gradient) order.
+#include "wk_direct_dev.h"
 
 #include <math.h>
 
@@ -37,48 +37,36 @@
 namespace wk {
 namespace {
 
-constexpr int kTrainBlock = 512;
 constexpr int kSlot = kNumWeights + 32;   // floats per workgroup slot: gradients, then the loss sum at [kNumWeights]
 
-// fragment-major weights (floats): forward A fragments [tile][step][64], step =
-// tap * CINP/4 + cb, lane l: co = 16 tile + (l & 15), ci = 4 cb + (l >> 4);
-// data-gradient A fragments [ci tile][step][64], step = tap * COUT/4 + cb,
-// lane l: ci = 16 tile + (l & 15), co = 4 cb + (l >> 4).
-constexpr int kTfW1 = 0;                        // [2][12][64]  (Cin 13 padded to 16)
-constexpr int kTfW2 = kTfW1 + 2 * 12 * 64;      // [4][24][64]
-constexpr int kTfW3 = kTfW2 + 4 * 24 * 64;      // [8][48][64]
-constexpr int kTbW2 = kTfW3 + 8 * 48 * 64;      // [2][48][64]
+// fragment-major weights (floats): the forward A fragments (wk_direct_dev.h),
+// then the data-gradient A fragments [ci tile][step][64], step = tap * COUT/4 +
+// cb, lane l: ci = 16 tile + (l & 15), co = 4 cb + (l >> 4).
+constexpr int kTbW2 = kDirectFwdPacked;         // [2][48][64]
 constexpr int kTbW3 = kTbW2 + 2 * 48 * 64;      // [4][96][64]
 constexpr int kTrainPacked = kTbW3 + 4 * 96 * 64;
 
-// LDS map (floats).  Row pitches are 4 mod 16 so the 16 rows of a B fragment
-// land in distinct banks.
-constexpr int kXP = 20, kP1P = 36, kP2P = 68, kP3P = 132;
-constexpr int sX = 0;                        // [66][20]
-constexpr int sP1 = sX + 66 * kXP;           // [34][36]
-constexpr int sP2 = sP1 + 34 * kP1P;         // [18][68]
-constexpr int sP3 = sP2 + 18 * kP2P;         // [8][132]   pooled conv3 output, row = pooled step
-constexpr int sR1 = sP3 + 8 * kP3P;          // [66][36]
+// LDS map (floats): the forward's images, then the backward pass's.
+constexpr int sR1 = kDirectLdsFloats;        // [66][36]
 constexpr int sR2 = sR1 + 66 * kP1P;         // [34][68]
 constexpr int sR3 = sR2 + 34 * kP2P;         // [18][132]
 constexpr int sD2 = sR3 + 18 * kP3P;         // [16][68]   first K half of dP2
 constexpr int sD1 = sD2 + 16 * kP2P;         // [32][36]   first K half of dP1
-constexpr int sG = sD1 + 32 * kP1P;          // [128]      mean over time
-constexpr int sH = sG + 128;                 // [64]       classifier.0 output after ReLU
-constexpr int sDG = sH + 64;                 // [4][128]   dG partial sums
-constexpr int sF2 = sDG + 512;               // [64]       classifier.2 weights
-constexpr int kLdsFloats = sF2 + 64;
+constexpr int sDG = sD1 + 32 * kP1P;         // [4][128]   dG partial sums
+constexpr int kLdsFloats = sDG + 512;
 static_assert(kLdsFloats * 4 <= 64 * 1024, "static LDS limit");
 
-__global__ void wk_train_pack_kernel(const float* __restrict__ w, float* __restrict__ pk) {
+// The first n floats of the fragment-major copy: kDirectFwdPacked (forward
+// order only) or kTrainPacked.
+__global__ void wk_pack_direct_kernel(const float* __restrict__ w, float* __restrict__ pk, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= kTrainPacked) return;
+  if (i >= n) return;
   int base, cin, cout, inner;   // inner: channels of the K dimension (padded)
   bool fwd;
   int wbase;
-  if (i < kTfW2) { base = kTfW1; cin = 13; cout = 32; inner = 16; fwd = true; wbase = kOffW1; }
-  else if (i < kTfW3) { base = kTfW2; cin = 32; cout = 64; inner = 32; fwd = true; wbase = kOffW2; }
-  else if (i < kTbW2) { base = kTfW3; cin = 64; cout = 128; inner = 64; fwd = true; wbase = kOffW3; }
+  if (i < kDfW2) { base = kDfW1; cin = 13; cout = 32; inner = 16; fwd = true; wbase = kOffW1; }
+  else if (i < kDfW3) { base = kDfW2; cin = 32; cout = 64; inner = 32; fwd = true; wbase = kOffW2; }
+  else if (i < kTbW2) { base = kDfW3; cin = 64; cout = 128; inner = 64; fwd = true; wbase = kOffW3; }
   else if (i < kTbW3) { base = kTbW2; cin = 32; cout = 64; inner = 64; fwd = false; wbase = kOffW2; }
   else { base = kTbW3; cin = 64; cout = 128; inner = 128; fwd = false; wbase = kOffW3; }
   const int j = i - base, l = j & 63, ns = 3 * inner / 4;
@@ -88,22 +76,10 @@ __global__ void wk_train_pack_kernel(const float* __restrict__ w, float* __restr
   pk[i] = (ci < cin && co < cout) ? w[wbase + (co * cin + ci) * 3 + tap] : 0.0f;
 }
 
-// One 16 x 16 tile of a forward convolution.  wf: the tile's fragments + lane;
-// img: the lane's B element of tap 0, step 0 (row t0 + (l & 15), column l >> 4).
-template <int CINP, int PITCH>
-__device__ __forceinline__ f32x4 conv_fwd_tile(const float* __restrict__ wf, const float* img) {
-  f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-  for (int tap = 0; tap < 3; ++tap)
-#pragma unroll
-    for (int cb = 0; cb < CINP / 4; ++cb)
-      acc = mfma4(wf[(tap * (CINP / 4) + cb) * 64], img[tap * PITCH + 4 * cb], acc);
-  return acc;
-}
-
-// ReLU + maxpool(2) of a forward tile: the route flags of its 16 positions and
-// the pooled values.  Lane l holds y[co0 .. co0 + 3][t]; the pool partner
-// t ^ 1 is lane l ^ 1.  TN = pooled steps (the floor pool drops the rest).
+// conv_layer_tile's epilogue: maxpool(2) + ReLU of a forward tile, the route
+// flags of its 16 positions and the pooled values.  Lane l holds
+// y[co0 .. co0 + 3][t]; the pool partner t ^ 1 is lane l ^ 1.  TN = pooled
+// steps (the floor pool drops the rest).
 template <int TN>
 __device__ __forceinline__ void epi_route_pool(const f32x4& acc, float* rrow, float* prow, int t, int lane) {
   const bool odd = lane & 1;
@@ -157,7 +133,7 @@ __device__ __forceinline__ void store_dw_tile(const f32x4& acc, float* dst, int 
   }
 }
 
-__global__ __launch_bounds__(kTrainBlock) void wk_train_grad_kernel(
+__global__ __launch_bounds__(kDirectBlock) void wk_train_grad_kernel(
     const float* __restrict__ feats, const float* __restrict__ labels, int64_t batch, const float* __restrict__ w,
     const float* __restrict__ pk, float* __restrict__ part, float* __restrict__ logits) {
   __shared__ __attribute__((aligned(16))) float sm[kLdsFloats];
@@ -165,18 +141,12 @@ __global__ __launch_bounds__(kTrainBlock) void wk_train_grad_kernel(
   const int ln = lane & 15, q = lane >> 4;
   const float inv_b = 1.0f / (float)batch;
 
-  for (int i = tid; i < kLdsFloats; i += kTrainBlock) sm[i] = 0.0f;
-  __syncthreads();
-  if (tid < 64) sm[sF2 + tid] = w[kOffF2 + tid];
-
   // classifier.0: thread (o, part) owns F1[o][16 part .. +16] and its gradient
   const int fo = tid >> 3, fpart = tid & 7;
   float f1[16], df1[16];
+  direct_setup<kLdsFloats>(sm, w, tid, f1);
 #pragma unroll
-  for (int j = 0; j < 16; ++j) {
-    f1[j] = w[kOffF1 + fo * 128 + 16 * fpart + j];
-    df1[j] = 0.0f;
-  }
+  for (int j = 0; j < 16; ++j) df1[j] = 0.0f;
   float df2 = 0.0f, loss = 0.0f;
   f32x4 dw3[12], dw2[3], dw1;
 #pragma unroll
@@ -184,68 +154,40 @@ __global__ __launch_bounds__(kTrainBlock) void wk_train_grad_kernel(
 #pragma unroll
   for (int n = 0; n < 3; ++n) dw2[n] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
   dw1 = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+  auto route_pool = [](auto layer, const f32x4& acc, int t, int c0, int l, float* prow) {
+    constexpr int L = decltype(layer)::value;
+    constexpr int R = L == 1 ? sR1 : L == 2 ? sR2 : sR3, PITCH = L == 1 ? kP1P : L == 2 ? kP2P : kP3P;
+    epi_route_pool<kConvSteps[L]>(acc, sm + R + (t + 1) * PITCH + c0, prow, t, l);
+  };
 
   for (int64_t clip = blockIdx.x; clip < batch; clip += gridDim.x) {
     // ---- input: [13][63] -> X[t + 1][ci]
     const float* x = feats + clip * (13 * 63);
-    for (int i = tid; i < 13 * 63; i += kTrainBlock) {
+    for (int i = tid; i < 13 * 63; i += kDirectBlock) {
       const int ci = i / 63, t = i - 63 * ci;
       sm[sX + (t + 1) * kXP + ci] = x[i];
     }
     const float y = labels[clip];
-    // the fragment loads are loop-invariant; hoisted out of the clip loop they
-    // would take several hundred VGPRs, so the base is made opaque per clip
-    const float* pkc = pk;
-    asm volatile("" : "+s"(pkc));
+    const float* pkc = per_clip_base(pk);
     __syncthreads();
 
-    // ---- forward conv1: 2 co tiles x 4 t tiles, one per wave
-    {
-      const int mt = wave & 1, nt = wave >> 1, t = 16 * nt + ln, c0 = 16 * mt + 4 * q;
-      const f32x4 acc = conv_fwd_tile<16, kXP>(pkc + kTfW1 + mt * 12 * 64 + lane, sm + sX + t * kXP + q);
-      epi_route_pool<31>(acc, sm + sR1 + (t + 1) * kP1P + c0, sm + sP1 + ((t >> 1) + 1) * kP1P + c0, t, lane);
-    }
+    // ---- forward conv1, conv2, conv3: the route image of layer L is R_L[t + 1][co]
+    conv_layer_tile<1>(pkc, sm, wave, lane, route_pool);
     __syncthreads();
-    // ---- forward conv2: 4 co tiles x 2 t tiles
-    {
-      const int mt = wave & 3, nt = wave >> 2, t = 16 * nt + ln, c0 = 16 * mt + 4 * q;
-      const f32x4 acc = conv_fwd_tile<32, kP1P>(pkc + kTfW2 + mt * 24 * 64 + lane, sm + sP1 + t * kP1P + q);
-      epi_route_pool<15>(acc, sm + sR2 + (t + 1) * kP2P + c0, sm + sP2 + ((t >> 1) + 1) * kP2P + c0, t, lane);
-    }
+    conv_layer_tile<2>(pkc, sm, wave, lane, route_pool);
     __syncthreads();
-    // ---- forward conv3: 8 co tiles x 1 t tile
-    {
-      const int t = ln, c0 = 16 * wave + 4 * q;
-      const f32x4 acc = conv_fwd_tile<64, kP2P>(pkc + kTfW3 + wave * 48 * 64 + lane, sm + sP2 + t * kP2P + q);
-      epi_route_pool<7>(acc, sm + sR3 + (t + 1) * kP3P + c0, sm + sP3 + (t >> 1) * kP3P + c0, t, lane);
-    }
+    conv_layer_tile<3>(pkc, sm, wave, lane, route_pool);
     __syncthreads();
     // ---- mean over the 7 pooled steps
-    if (tid < 128) {
-      float s = 0.0f;
-#pragma unroll
-      for (int p = 0; p < 7; ++p) s += sm[sP3 + p * kP3P + tid];
-      sm[sG + tid] = s / 7.0f;
-    }
+    if (tid < 128) gap_channel(sm, tid);
     __syncthreads();
     // ---- classifier.0 + ReLU: 8 threads per output row
     float g[16];
-    {
-      float s = 0.0f;
-#pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        g[j] = sm[sG + 16 * fpart + j];
-        s = fmaf(f1[j], g[j], s);
-      }
-      s += dpp<0xB1>(s);
-      s += dpp<0x4E>(s);
-      s += dpp<0x141>(s);
-      if (fpart == 0) sm[sH + fo] = fmaxf(s, 0.0f);
-    }
+    classifier0(sm, tid, f1, g);
     __syncthreads();
     // ---- classifier.2, loss, dz: every wave computes the same z
-    const float hv = sm[sH + lane];
-    const float z = wave_sum(sm[sF2 + lane] * hv);
+    float hv;
+    const float z = classifier2(sm, lane, hv);
     const float dz = (1.0f / (1.0f + expf(-z)) - y) * inv_b;
     if (tid == 0) {
       loss += fmaxf(z, 0.0f) - z * y + log1pf(expf(-fabsf(z)));
@@ -268,7 +210,7 @@ __global__ __launch_bounds__(kTrainBlock) void wk_train_grad_kernel(
     }
     __syncthreads();
     // ---- dY3 = route * dG / 7 (pre-pool rows 0..13)
-    for (int i = tid; i < 14 * 128; i += kTrainBlock) {
+    for (int i = tid; i < 14 * 128; i += kDirectBlock) {
       const int t = i >> 7, co = i & 127;
       const float dg = ((sm[sDG + co] + sm[sDG + 128 + co]) + (sm[sDG + 256 + co] + sm[sDG + 384 + co])) / 7.0f;
       sm[sR3 + (t + 1) * kP3P + co] *= dg;
@@ -381,13 +323,19 @@ __global__ void wk_train_adamw_kernel(float* __restrict__ p, float* __restrict__
 }
 
 }  // namespace
+
+hipError_t launch_pack_direct(const float* w, float* pk, int count, hipStream_t stream) {
+  wk_pack_direct_kernel<<<(count + 255) / 256, 256, 0, stream>>>(w, pk, count);
+  return hipGetLastError();
+}
+
 }  // namespace wk
 
 struct wk_trainer {
   int device = 0;
   int grid_cap = 512;        // workgroups per gradient launch
   float* d_w = nullptr;      // [WK_NUM_WEIGHTS] current weights
-  float* d_pk = nullptr;     // fragment-major copy (wk_train_pack_kernel)
+  float* d_pk = nullptr;     // fragment-major copy (launch_pack_direct)
   float* d_g = nullptr;      // last gradients
   float* d_m = nullptr;      // AdamW first / second moments
   float* d_v = nullptr;
@@ -472,8 +420,9 @@ wk_status wk_trainer_grad(wk_trainer* t, const float* d_feats, const float* d_la
         return e == hipErrorOutOfMemory ? wk::fail(WK_ERR_NO_MEMORY, "wk_trainer_grad: workspace") : hip_fail(e, "wk_trainer_grad: workspace");
       t->part_slots = grid;
     }
-    wk::wk_train_pack_kernel<<<(wk::kTrainPacked + 255) / 256, 256, 0, st>>>(t->d_w, t->d_pk);
-    wk::wk_train_grad_kernel<<<grid, wk::kTrainBlock, 0, st>>>(d_feats, d_labels, batch, t->d_w, t->d_pk, t->d_part,
+    if ((e = wk::launch_pack_direct(t->d_w, t->d_pk, wk::kTrainPacked, st)) != hipSuccess)
+      return hip_fail(e, "wk_trainer_grad launch");
+    wk::wk_train_grad_kernel<<<grid, wk::kDirectBlock, 0, st>>>(d_feats, d_labels, batch, t->d_w, t->d_pk, t->d_part,
                                                                d_logits_or_null);
     wk::wk_train_reduce_kernel<<<(wk::kNumWeights + 1 + 255) / 256, 256, 0, st>>>(t->d_part, grid, batch, t->d_g,
                                                                                  d_grads_or_null, d_loss);

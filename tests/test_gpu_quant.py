@@ -94,6 +94,25 @@ def test_calibration_counts_against_float64(fp32_model, g24, ref24, xiaoa_sd):
     assert wakeword.calibrate(m8, g24) == wakeword.calibrate(xiaoa_sd, g24) == wakeword.calibrate(fp32_model, g24)
 
 
+def test_calibration_and_trainer_share_one_forward(gpu, g24, xiaoa_sd):
+    """Calibration and the trainer run the same direct-form forward (csrc/wk_direct_dev.h), so the logit maximum
+    calibration observes has the bits of the trainer's |logit|: clip by clip (B = 1, one workgroup, one clip) and over
+    the 24 clips at once (a multi-clip walk), for xiaoa's weights and for a default initialisation."""
+    import wakeword
+    from wakeword.train import default_init
+    labels = (np.arange(24) % 2).astype(np.float32)
+    for name, sd in (("xiaoa", xiaoa_sd), ("default_init(0)", default_init(0))):
+        logit = np.abs(wakeword.Trainer(sd).grad(g24, labels)[1].cpu().numpy())
+        assert logit.dtype == np.float32 and logit.shape == (24,)
+        for i in (0, 11, 23):
+            _, st = wakeword.calibrate(sd, g24[i:i + 1], return_stats=True)
+            print(name, "clip", i, "trainer |logit|", logit[i].view(np.uint32), "calibration", st["max_abs"][6].view(np.uint32))
+            assert st["max_abs"][6].view(np.uint32) == logit[i].view(np.uint32), (name, i)
+        _, st = wakeword.calibrate(sd, g24, return_stats=True)
+        print(name, "24 clips: trainer max |logit|", logit.max().view(np.uint32), "calibration", st["max_abs"][6].view(np.uint32))
+        assert st["max_abs"][6].view(np.uint32) == logit.max().view(np.uint32), name
+
+
 def test_run_time_exponents_bit_exact_mfma(gpu, xiaoa_sd, cal24):
     Q.check_entry_points(xiaoa_sd, cal24)
 
