@@ -1,0 +1,118 @@
+// wk_ctc_dev.h -- what the units of the GRU-CTC head share (internal): the
+// model's fixed sizes, the fp16 fragment vectors, one wave reduction, and the
+// launchers wk_ctc.hip (the C ABI, no kernels) calls into the per-stage units:
+//
+//   wk_ctc_logmel.hip  X1   log-mel front end + z-score, its host tables
+//   wk_ctc_dense.hip   X2a  encoder (fp32 / fp16), the block GEMM, fp16 <-> fp32 copy
+//   wk_ctc_gru.hip     X2b  the three recurrences and their weight packers
+//   wk_ctc_out.hip     X2c / X3  output layer + argmax kernels, re-score, greedy decode
+//
+// Layout constants stay with the kernel that defines the layout: each packer
+// and each grid computation sits in the kernel's own unit, so none is needed
+// here.  A launcher that only enqueues kernels returns nothing: a launch error
+// is picked up by the one hipGetLastError that ends each wk_ctc_* entry point.
+// The GEMM entry points check their shapes and report like the ABI does.
+#pragma once
+#include <hip/hip_fp16.h>
+
+#include <vector>
+
+#include "wk_cnn_dev.h"
+#include "wk_kernels.h"
+
+namespace wk {
+
+constexpr int kNfft = 400, kHop = 160, kBins = kNfft / 2 + 1, kMels = 80, kH = 128;
+
+typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+
+// Sum over the four lanes l, l ^ 16, l ^ 32, l ^ 48 (a row's four 16-lane
+// groups), in every lane: gfx950's v_permlane16/32_swap exchange rows in the
+// VALU (with both operands the same register, the two results are the
+// lane's and its partner's values), no LDS round trip as __shfl_xor costs.
+__device__ __forceinline__ float sum_rows4(float v) {
+  const auto p = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  v = __uint_as_float(p[0]) + __uint_as_float(p[1]);
+  const auto q = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  return __uint_as_float(q[0]) + __uint_as_float(q[1]);
+}
+
+// ---- wk_ctc_logmel.hip ------------------------------------------------------
+// Host tables of ctc_logmel_fft2_kernel: periodic Hann(400), the four-step
+// twiddles W400^(n2 k1) [20 k1][20 n2] complex, the per-lane padded mel weights
+// x 1/4 ([64][kMelW1] then [64][kMelW2]) and their window start bins ([64] then
+// [64]).  False when the filterbank does not fit the kernel's fixed windows.
+struct CtcLogmelTables {
+  std::vector<float> win, tw, melw;
+  std::vector<int> melws;
+};
+bool ctc_logmel_tables(CtcLogmelTables* t);
+// The log-mel kernel's launch: at most one 12-wave workgroup per CU, each wave
+// a contiguous range of R passes; MS statistics slots per wave (the most
+// utterances 6 R rows can touch), slots = waves x MS.
+struct CtcLogmelLayout {
+  unsigned grid;
+  int64_t R;
+  int MS;
+  int64_t slots;
+};
+CtcLogmelLayout ctc_logmel_layout(int n_cu, int64_t rows, int T);
+// part != null: the features stay raw and each wave leaves its z-score partials there.
+void launch_ctc_logmel(const float* audio, int64_t stride, int n_valid, int n_pad, int T, int64_t rows, const float* win,
+                       const float* tw, const float* melw, const int* melws, float* feats, const CtcLogmelLayout& lay,
+                       float2* part, hipStream_t st);
+// The z-score of [batch][T][80] features in place, or with part (the log-mel launch's) only its {mean, 1/std} to zs.
+void launch_ctc_zscore(float* feats, int64_t batch, int T, const CtcLogmelLayout& lay, const float2* part, float2* zs,
+                       hipStream_t st);
+
+// ---- wk_ctc_dense.hip -------------------------------------------------------
+// feats [B][T][80] -> out: fp32 rows in the same order, or (f16) fp16 time-major rows t B + b, where zs != null
+// z-scores the raw feature rows as they load.
+void launch_ctc_encoder(bool f16, const float* feats, int B, int T, const float* w, const float* bias, const float* gamma,
+                        const float* beta, const float2* zs, void* out, int n_cu, hipStream_t st);
+// Row-major C[M][N] (fp32, or fp16 with c16) = A[M][K] * W[N][K]^T with A, W
+// fp32 or fp16 (fp32 accumulate), on `st`.
+wk_status ctc_gemm_nt(hipStream_t st, int64_t M, int64_t N, int64_t K, const void* A, const void* W, void* C, bool f16,
+                      bool c16 = false);
+// fp32 best[row] = first argmax of A[M][K] W[N][K]^T + bias (K % 16 == 0),
+// with keys [M] as scratch: zero, GEMM + atomic argmax, decode.
+wk_status ctc_gemm_argmax(hipStream_t st, int64_t M, int64_t N, int64_t K, const float* A, const float* W,
+                          const float* bias, unsigned long long* keys, int* best);
+void launch_ctc_convert(const __half* in, float* out, int64_t n, int n_cu, hipStream_t st);
+void launch_ctc_convert(const float* in, __half* out, int64_t n, int n_cu, hipStream_t st);
+
+// ---- wk_ctc_gru.hip ---------------------------------------------------------
+// One layer, both directions.  W_hh [2 dir][384][128] fp32 -> the fragment
+// layouts of ctc_gru_kernel ([2][24 tiles][32 k-steps][64 lanes]) and
+// ctc_gru16_kernel ([2][24 tiles][8 k-steps][64 lanes][4]).
+std::vector<float> ctc_pack_whh(const float* whh);
+std::vector<float> ctc_pack_whh16(const float* whh);
+// ctc_gru16x_kernel's 16x16x32 A fragments of src [2 dir][3 gates x 128][K]:
+// [dir][gate][wave][K/32 k-steps][lane][8], gate g's rows times scale[g].
+constexpr double kCtcGateScale[3] = {-1.4426950408889634, -1.4426950408889634, 2.8853900817779268};
+std::vector<float> ctc_pack_frag32(const float* src, int K, const double (&scale)[3]);
+// Gate inputs gi [rows][768] from ctc_gemm_nt: fp32 tensors and ctc_pack_whh's weights, or (f16) fp16 time-major
+// tensors and ctc_pack_whh16's.
+void launch_ctc_gru(bool f16, const void* gi, const void* whh_pk, const float* bih, const float* bhh, int64_t B, int T,
+                    void* out, hipStream_t st);
+// Input projection fused in: x time-major [T][B][din] fp16, din = 128 or 256.
+void launch_ctc_gru16x(int din, const __half* x, const __half* wih16x_pk, const __half* whh16x_pk, const float* bih,
+                       const float* bhh, int64_t B, int T, __half* out, hipStream_t st);
+
+// ---- wk_ctc_out.hip ---------------------------------------------------------
+// bias + log_softmax + argmax over materialised logits (fp32, or fp16 with
+// f16); log_probs and best may be null; tm_B > 0: the logits rows are time-major.
+void launch_ctc_argmax(bool f16, const void* logits, const float* bias, int64_t rows, int V, float* log_probs, int* best,
+                       int tm_B, int T, hipStream_t st);
+// The fused fp16 output layer + argmax.  logits != null also stores the fp16
+// logits; fold picks ctc_out_decode16_kernel where it applies (V <= 4096, no logits).
+constexpr bool ctc_out_keyed(int V) { return V <= 16 * 256; }   // the tag holds kOutCF tile + cf in 8 bits
+void launch_ctc_out16(const __half* y, const __half* w16, const float* bias, int64_t rows, int V, __half* logits, int* best,
+                      int* best2, bool fold, hipStream_t st);
+void launch_ctc_rescore(const __half* y, const float* w, const float* bias, int64_t rows, int* best, const int* best2,
+                        hipStream_t st);
+void launch_ctc_greedy(const int* best, int64_t B, int T, int* tokens, int* lengths, int tm, hipStream_t st);
+void launch_ctc_pred(const int* best, int64_t B, int T, int tm, int* pred, hipStream_t st);
+
+}  // namespace wk

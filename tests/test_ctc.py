@@ -253,15 +253,26 @@ def test_ctc_transcribe_one_call(ctc, precision):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("n_samples", [800, 960, 1920, 8000])
-def test_ctc_transcribe_short_utterances(ctc, n_samples):
+@pytest.mark.parametrize("n_samples,out16_vocab", [(800, 0), (960, 0), (1920, 0), (8000, 0), (8000, V), (8000, 4100)],
+                         ids=["800", "960", "1920", "8000", "8000-out16", "8000-out16-V4100"])
+def test_ctc_transcribe_short_utterances(ctc, n_samples, out16_vocab, monkeypatch):
     """The folded z-score at small T (6, 7, 13, 51 frames): log-mel passes of
     6 rows start mid-utterance and straddle two utterances in every pattern;
     the fp16 one-call path must give the oracle's argmax on confident frames
-    for all 11 utterances."""
+    for all 11 utterances.  out16: the same bound for the fp32 path with the
+    fp16 output kernel (WAKEWORD_CTC_MIX=out16, re-scoring on), tagged
+    (V <= 4096) and untagged -- the two launches of that path no other test
+    reaches."""
     import wakeword
     m, _ = ctc
-    g = wakeword.CTCModel(CO.flat_weights(m), V, precision="fp16")
+    if out16_vocab:
+        if out16_vocab != V:
+            m = CO.make_model(out16_vocab, seed=11)
+        monkeypatch.setenv("WAKEWORD_CTC_MIX", "out16")
+        g = wakeword.CTCModel(CO.flat_weights(m), out16_vocab, precision="fp32")
+        monkeypatch.delenv("WAKEWORD_CTC_MIX")
+    else:
+        g = wakeword.CTCModel(CO.flat_weights(m), V, precision="fp16")
     B, T = 11, 1 + n_samples // 160
     x = O.synth_clips(31, 0, B, n_samples)
     tok, ln = g.decode_audio(x, n_samples=n_samples)
