@@ -428,6 +428,7 @@ wk_status ctc_forward(wk_ctc* c, const float* d_feats, int64_t batch, int32_t T,
       launch_ctc_convert(c->y1h, c->y1, rows * 2 * kH, c->n_cu, st);
       s = stage_out32(f, c->y1, nullptr);
     } else if (!f16 && c->mix == 2) {   // attribution: the fp32 path's y1, rounded, through the fp16 output kernel
+      if (d_log_probs) return fail(WK_ERR_UNSUPPORTED, "WAKEWORD_CTC_MIX=out16 decodes only (no log-probs)");
       launch_ctc_convert(c->y1, c->y1h, rows * 2 * kH, c->n_cu, st);
       s = stage_out16(f, c->y1h, nullptr, false);
     } else {

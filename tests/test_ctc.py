@@ -115,6 +115,7 @@ def test_ctc_fp16_gemm_mode(ctc):
     assert np.abs((lp - ref_lp).numpy()).max() <= 0.05
     top2 = torch.topk(ref_lp, 2, dim=-1).values
     ok = (top2[..., 0] - top2[..., 1]) > 0.2
+    assert ok.float().mean() > 0.1       # the gate keeps a real share of the frames
     assert (lp.argmax(-1) == ref_lp.argmax(-1))[ok].all()
 
 
@@ -140,6 +141,7 @@ def test_ctc_fp16_ragged_vocab(vocab):
     assert lp.shape[-1] == vocab and np.abs((lp - ref_lp).numpy()).max() <= 0.05
     top2 = torch.topk(ref_lp, 2, dim=-1).values
     ok = (top2[..., 0] - top2[..., 1]) > 0.2
+    assert ok.float().mean() > 0.1       # the gate keeps a real share of the frames
     assert (lp.argmax(-1) == ref_lp.argmax(-1))[ok].all()
 
 
@@ -242,6 +244,7 @@ def test_ctc_transcribe_one_call(ctc, precision):
             ref_lp = m(feats)
         top2 = torch.topk(ref_lp, 2, dim=-1).values
         ok = (top2[..., 0] - top2[..., 1]) > 0.2
+        assert ok.float().mean() > 0.1
         live = [0, 1, 2, 4, 5, 6]
         assert (pred[live] == ref_lp.argmax(-1))[ok].all()
         assert (pred[live] == pred2[live])[ok].all()
@@ -258,8 +261,9 @@ def test_ctc_transcribe_one_call(ctc, precision):
 def test_ctc_transcribe_short_utterances(ctc, n_samples, out16_vocab, monkeypatch):
     """The folded z-score at small T (6, 7, 13, 51 frames): log-mel passes of
     6 rows start mid-utterance and straddle two utterances in every pattern;
-    the fp16 one-call path must give the oracle's argmax on confident frames
-    for all 11 utterances.  out16: the same bound for the fp32 path with the
+    the fp16 one-call path must give the oracle's argmax on the confident
+    frames of the 11 utterances (more than a tenth of all frames; an utterance
+    may have none: tests/test_gpu_ctc_parity.py covers every utterance).  out16: the same bound for the fp32 path with the
     fp16 output kernel (WAKEWORD_CTC_MIX=out16, re-scoring on), tagged
     (V <= 4096) and untagged -- the two launches of that path no other test
     reaches."""
@@ -281,6 +285,7 @@ def test_ctc_transcribe_short_utterances(ctc, n_samples, out16_vocab, monkeypatc
         ref_lp = m(CO.features(torch.from_numpy(x)))
     top2 = torch.topk(ref_lp, 2, dim=-1).values
     ok = (top2[..., 0] - top2[..., 1]) > 0.2
+    assert ok.float().mean() > 0.1
     assert (pred == ref_lp.argmax(-1))[ok].all()
     assert int(ln.min()) >= 0 and int(ln.max()) <= T
 
@@ -377,6 +382,7 @@ def test_ctc_fp16_fused_projection_matches_gemm_path(B, monkeypatch):
     assert np.abs((lp_g - ref_lp).numpy()).max() <= 0.05
     top2 = torch.topk(ref_lp, 2, dim=-1).values
     ok = (top2[..., 0] - top2[..., 1]) > 0.2
+    assert ok.float().mean() > 0.1
     assert (lp_f.argmax(-1) == ref_lp.argmax(-1))[ok].all()
     # fp32 gate pre-activations: the fused path is at least as close to the oracle
     assert np.abs((lp_f - ref_lp).numpy()).mean() <= np.abs((lp_g - ref_lp).numpy()).mean() * 1.05
