@@ -34,7 +34,9 @@ EXPORTS = ("wk_create", "wk_destroy", "wk_mfcc", "wk_cnn", "wk_forward", "wk_syn
            "wk_ctc_profile", "wk_ctc_stage_times", "wk_ctc_transcribe", "wk_esp_mfcc_create", "wk_esp_mfcc_run",
            "wk_esp_mfcc_destroy", "wk_scan", "wk_scan_workspace_bytes", "wk_trainer_create", "wk_trainer_destroy",
            "wk_trainer_grad", "wk_trainer_step", "wk_trainer_weights", "wk_quant_spec_default", "wk_set_quant",
-           "wk_get_quant", "wk_quant_weights", "wk_calibrate_workspace_bytes", "wk_calibrate")
+           "wk_get_quant", "wk_quant_weights", "wk_calibrate_workspace_bytes", "wk_calibrate",
+           "wk_ctc_loss_workspace_bytes", "wk_ctc_loss")
+WK_CTC_REDUCTION = {"none": 0, "sum": 1, "mean": 2}
 WK_NUM_INT8_WEIGHTS = 3 * 13 * 32 + 3 * 32 * 64 + 3 * 64 * 128 + 128 * 64 + 64
 WK_QUANT_TENSORS = 7
 WK_QUANT_BINS = 32
@@ -139,6 +141,11 @@ def _declare(L):
         L.wk_calibrate_workspace_bytes.argtypes = [i64, C.POINTER(C.c_size_t)]
         L.wk_calibrate.argtypes = [vp, vp, i64, C.c_double, i32, vp, C.c_size_t, C.POINTER(WkQuantSpec),
                                    C.POINTER(WkCalibStats), vp]
+    if hasattr(L, "wk_ctc_loss"):   # (absent from older libraries loaded for A/B timing)
+        L.wk_ctc_loss_workspace_bytes.argtypes = [i64, i32, i32]
+        L.wk_ctc_loss_workspace_bytes.restype = i64
+        L.wk_ctc_loss.argtypes = [vp, i64, i32, i32, vp, i32, vp, vp, i32, i32, i32, C.c_float, vp, vp, vp, vp, i32, vp]
+        L.wk_ctc_loss.restype = i32
     for name in ("wk_create", "wk_destroy", "wk_mfcc", "wk_cnn", "wk_forward", "wk_synth_clips", "wk_normalize",
                  "wk_stream_create", "wk_stream_destroy", "wk_stream_reset", "wk_stream_push", "wk_ctc_create",
                  "wk_ctc_destroy", "wk_ctc_features", "wk_ctc_forward", "wk_wav_read", "wk_wav_load_batch",

@@ -7,6 +7,8 @@ inference surface on the HIP path (wk_ctc_* in the C ABI).
     tokens = model.transcribe(audio)                     # both
     texts = model.decode_predictions(log_probs)          # ctc.py:453-471 (idx_to_char map)
     texts = model.transcribe_text(audio)                 # device decode, then the map
+    loss = wakeword.ctc_loss(log_probs, targets, input_lengths, target_lengths)   # nn.CTCLoss(blank=0), ctc.py:369
+    loss = model.loss(feats, targets, input_lengths, target_lengths)              # validation loss, ctc.py:409-425
 
 A state dict is bound BY NAME: its keys must be exactly GRU_CTC_Model's
 (ctc_state_dict_spec(), ctc.py:119-146: audio_encoder.{0,1}, gru.*_l{k}[_reverse],
@@ -124,6 +126,122 @@ def decode_predictions(log_probs, idx_to_char: Mapping[int, str]) -> List[str]:
     return tokens_to_text(greedy_tokens(log_probs), idx_to_char)
 
 
+MAX_LABEL_LEN = 255             # wk_ctc_loss: 2 S + 1 <= 511 states, 8 registers per lane
+
+
+def pad_targets(targets, target_lengths):
+    """nn.CTCLoss's two target forms as one padded (B, max(S_max, 1)) int32
+    tensor: 2-D (B, S) targets as they are (on their device, no sync); 1-D
+    concatenated targets split by target_lengths and zero-padded, on the host
+    (lengths on the device are read back)."""
+    import torch
+    t = torch.as_tensor(targets)
+    if t.dim() == 2:
+        return t.to(torch.int32) if t.shape[1] > 0 else torch.zeros((t.shape[0], 1), dtype=torch.int32, device=t.device)
+    if t.dim() != 1:
+        raise ValueError(f"targets must be (B, S) or 1-D concatenated, got {tuple(t.shape)}")
+    lens = [int(n) for n in torch.as_tensor(target_lengths).reshape(-1).tolist()]
+    if min(lens, default=0) < 0 or sum(lens) != t.numel():
+        raise ValueError(f"target_lengths sum to {sum(lens)}, targets hold {t.numel()}")
+    t = t.cpu().to(torch.int32)
+    out = torch.zeros((len(lens), max(max(lens, default=0), 1)), dtype=torch.int32)
+    off = 0
+    for b, n in enumerate(lens):
+        out[b, :n] = t[off:off + n]
+        off += n
+    return out
+
+
+_loss_fn = None
+
+
+def _ctc_loss_fn():
+    """The autograd function behind ctc_loss (built on first use: torch is
+    imported lazily throughout this package)."""
+    global _loss_fn
+    if _loss_fn is not None:
+        return _loss_fn
+    import torch
+
+    def ptr(t):
+        return C.c_void_p(t.data_ptr())
+
+    class CTCLossFn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, lp, labels, in_len, lab_len, max_label_len, reduction, zero_infinity):
+            B, T, V = lp.shape
+            L = lib()
+            nbytes = L.wk_ctc_loss_workspace_bytes(B, T, max_label_len)
+            if nbytes <= 0:
+                raise _lib.WakewordError(f"wk_ctc_loss: unsupported shape (B={B}, T={T}, max label length {max_label_len} "
+                                         f"> {MAX_LABEL_LEN}?)")
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=lp.device)
+            nll = torch.empty(B, dtype=torch.float32, device=lp.device)
+            loss = torch.empty(1, dtype=torch.float32, device=lp.device)
+            grad = torch.empty_like(lp) if ctx.needs_input_grad[0] else None
+            check(L.wk_ctc_loss(ptr(lp), B, T, V, ptr(labels), labels.shape[1], ptr(in_len), ptr(lab_len), max_label_len,
+                                _lib.WK_CTC_REDUCTION[reduction], int(zero_infinity), 1.0, ptr(ws), ptr(nll), ptr(loss),
+                                ptr(grad) if grad is not None else None, lp.device.index,
+                                C.c_void_p(torch.cuda.current_stream(lp.device).cuda_stream)), "wk_ctc_loss")
+            ctx.per_utterance = reduction == "none"
+            ctx.save_for_backward(grad)
+            return nll if reduction == "none" else loss.reshape(())
+
+        @staticmethod
+        def backward(ctx, grad_output):
+            (grad,) = ctx.saved_tensors
+            if ctx.per_utterance:
+                grad_output = grad_output.reshape(-1, 1, 1)
+            return grad * grad_output, None, None, None, None, None, None
+
+    _loss_fn = CTCLossFn
+    return _loss_fn
+
+
+def ctc_loss(log_probs, targets, input_lengths, target_lengths, reduction: str = "mean", zero_infinity: bool = False,
+             batch_first: bool = False):
+    """F.ctc_loss(..., blank=0) on the HIP device (wk_ctc_loss; ctc.py:369,
+    :394, :416): log_probs (T, B, V) float32 as the reference passes them, or
+    (B, T, V) with batch_first=True -- what CTCModel.decode returns and what
+    the kernels read, so that form is used without a copy; targets (B, S)
+    padded or 1-D concatenated; lengths as tensors or sequences.  Runs on the
+    current stream.  When log_probs requires grad the gradient is computed in
+    this call (torch's native convention, exact through log_softmax's backward)
+    and backward() only scales it by grad_output (per utterance for
+    reduction="none")."""
+    import torch
+    if reduction not in _lib.WK_CTC_REDUCTION:
+        raise ValueError(f"reduction must be 'none', 'sum' or 'mean', got {reduction!r}")
+    if not (torch.is_tensor(log_probs) and log_probs.is_cuda and log_probs.dtype == torch.float32 and log_probs.dim() == 3):
+        raise ValueError("log_probs must be a 3-D float32 tensor on the HIP device")
+    lp = (log_probs if batch_first else log_probs.transpose(0, 1)).contiguous()
+    B = lp.shape[0]
+    labels = pad_targets(targets, target_lengths).to(lp.device).contiguous()
+    in_len = torch.as_tensor(input_lengths).reshape(-1).to(device=lp.device, dtype=torch.int32).contiguous()
+    lab_len = torch.as_tensor(target_lengths).reshape(-1).to(device=lp.device, dtype=torch.int32).contiguous()
+    if labels.shape[0] != B or in_len.numel() != B or lab_len.numel() != B:
+        raise ValueError(f"batch of {B}: targets {tuple(labels.shape)}, {in_len.numel()} input and {lab_len.numel()} target lengths")
+    max_label_len = labels.shape[1]
+    if max_label_len > MAX_LABEL_LEN:      # padding wider than the kernels' limit: the longest label decides (a host sync)
+        max_label_len = int(lab_len.max())
+    return _ctc_loss_fn().apply(lp, labels, in_len, lab_len, max_label_len, reduction, bool(zero_infinity))
+
+
+class CTCLoss:
+    """nn.CTCLoss(blank=0)'s call form over ctc_loss (stateless: no parameters)."""
+
+    def __init__(self, reduction: str = "mean", zero_infinity: bool = False, batch_first: bool = False):
+        if reduction not in _lib.WK_CTC_REDUCTION:
+            raise ValueError(f"reduction must be 'none', 'sum' or 'mean', got {reduction!r}")
+        self.reduction, self.zero_infinity, self.batch_first = reduction, zero_infinity, batch_first
+
+    def forward(self, log_probs, targets, input_lengths, target_lengths):
+        return ctc_loss(log_probs, targets, input_lengths, target_lengths, self.reduction, self.zero_infinity,
+                        self.batch_first)
+
+    __call__ = forward
+
+
 class CTCModel:
     def __init__(self, weights: Union[np.ndarray, Mapping[str, np.ndarray]], vocab: int, device: int = 0,
                  precision: str = "fp32", idx_to_char: Optional[Mapping[int, str]] = None):
@@ -227,6 +345,12 @@ class CTCModel:
         if m is None:
             raise ValueError("no idx_to_char map: pass one here or to CTCModel(...)")
         return m
+
+    def loss(self, feats, targets, input_lengths, target_lengths, reduction: str = "mean"):
+        """The validation loss of ctc.py:409-425: decode(feats,
+        return_log_probs=True), then ctc_loss on the (B, T, V) log-probs."""
+        _, _, lp = self.decode(feats, return_log_probs=True)
+        return ctc_loss(lp, targets, input_lengths, target_lengths, reduction=reduction, batch_first=True)
 
     def decode_predictions(self, log_probs, idx_to_char: Optional[Mapping[int, str]] = None) -> List[str]:
         """THCHS30Trainer.decode_predictions (ctc.py:453-471) with this model's map."""

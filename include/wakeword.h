@@ -312,6 +312,38 @@ wk_status wk_ctc_stage_times(wk_ctc* c, double* ms_sum /* [WK_CTC_N_STAGES] */, 
  * must be that call's (else WK_ERR_INVALID_ARG); stream-ordered after it. */
 wk_status wk_ctc_frame_argmax(wk_ctc* c, int64_t batch, int32_t T, int32_t* d_pred, void* stream);
 
+/* ---- CTC loss and its gradient (nn.CTCLoss(blank=0); ctc.py:369, :380-425) ---
+ * d_log_probs [batch][T][vocab] fp32 (the layout wk_ctc_forward writes),
+ * d_labels [batch][label_stride] int32, d_input_lengths / d_label_lengths
+ * [batch] int32 on the device: trusted to lie in [0, T] / [0, max_label_len]
+ * and clamped to them.  Outputs: d_nll [batch], each utterance's negative
+ * log-likelihood, and d_loss [1], their reduction: the sum (NONE and SUM; with
+ * NONE the result proper is d_nll) or mean_b(nll_b / max(S_b, 1)) (MEAN).
+ * d_grad_or_null [batch][T][vocab], when given, receives
+ *   g[b,t,v] = exp(lp[b,t,v]) - exp(lse_{s: l'_s = v}(alpha_t(s) + beta_t(s)) + nll_b - lp[b,t,v])
+ * (torch's native CTC backward: the gradient at the logits under log_softmax,
+ * which also passes unchanged through log_softmax's backward), times
+ * grad_scale, and with MEAN times 1 / (batch * max(S_b, 1)); exactly 0 at
+ * t >= d_input_lengths[b].  An utterance without a valid alignment (T_b < S_b +
+ * adjacent repeats, or a label outside [1, vocab), which is never used as an
+ * index) has nll = +inf, or 0 with zero_infinity; its gradient rows are 0 and
+ * the other utterances are unaffected.  fp32 arithmetic in log space; nothing
+ * is accumulated by atomics, so equal inputs give equal bits.
+ * Limits: max_label_len <= 255, vocab <= 65536, batch * T <= 2^28; beyond
+ * them, and for a null pointer, batch, T or vocab <= 0, label_stride <
+ * max_label_len or an unknown reduction: WK_ERR_INVALID_ARG before any device
+ * work (wk_ctc_loss_workspace_bytes then returns 0).  Stream-ordered, no host
+ * synchronisation; d_workspace (16-byte aligned, wk_ctc_loss_workspace_bytes)
+ * is the caller's, so concurrent calls with workspaces of their own are safe. */
+enum { WK_CTC_REDUCTION_NONE = 0, WK_CTC_REDUCTION_SUM = 1, WK_CTC_REDUCTION_MEAN = 2 };
+int64_t wk_ctc_loss_workspace_bytes(int64_t batch, int32_t T, int32_t max_label_len);
+wk_status wk_ctc_loss(const float* d_log_probs, int64_t batch, int32_t T, int32_t vocab,
+                      const int32_t* d_labels, int32_t label_stride,
+                      const int32_t* d_input_lengths, const int32_t* d_label_lengths,
+                      int32_t max_label_len, int32_t reduction, int32_t zero_infinity, float grad_scale,
+                      void* d_workspace, float* d_nll, float* d_loss, float* d_grad_or_null,
+                      int32_t device, void* stream);
+
 /* ---- WAV ingest and waveform augmentation (host only) ---
  * No device work: these fill caller (e.g. pinned) host buffers for the H2D copy. */
 typedef struct {
