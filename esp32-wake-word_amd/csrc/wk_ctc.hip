@@ -15,9 +15,12 @@
 #include <string.h>
 
 #include <array>
+#include <memory>
+#include <new>
 #include <type_traits>
 
 #include "wk_ctc_dev.h"
+#include "wk_devmem.h"
 
 using namespace wk;
 
@@ -26,17 +29,17 @@ struct wk_ctc {
   int n_cu;
   bool f16;             // precision 1: GEMM operands in fp16 (fp32 accumulate); recurrence fp32
   // weights (device)
-  float *enc_w, *enc_b, *ln_g, *ln_b;
-  float* wih[2];        // per layer: [768][Din] (fwd rows then reverse rows)
-  float* bih[2];        // per layer: [768]
-  float* bhh[2];        // per layer: [768]
-  float* whh_pk[2];     // per layer: [2 dir][24 tiles][32 k-steps][64 lanes]
-  float *out_w, *out_b; // [V][256], [V]
-  float* zero_b;        // [V] zeros: the log_softmax kernel's bias in fp16 mode (the logits carry theirs)
-  __half* wih16[2];     // fp16 copies (precision 1)
-  __half* whh16_pk[2];  // per layer: [2 dir][24 tiles][8 k-steps][64 lanes][4]
-  __half* whh16x_pk[2]; // per layer: [2 dir][3 gates][8 waves][4 k-steps][64 lanes][8] (W_hh as 16x16x32 fragments, gate-scaled)
-  __half* wih16x_pk[2]; // per layer: [2 dir][3 gates][8 waves][din/32 k-steps][64 lanes][8] (fused-projection GRU, gate-scaled)
+  DevBuf<float> enc_w, enc_b, ln_g, ln_b;
+  DevBuf<float> wih[2];        // per layer: [768][Din] (fwd rows then reverse rows)
+  DevBuf<float> bih[2];        // per layer: [768]
+  DevBuf<float> bhh[2];        // per layer: [768]
+  DevBuf<float> whh_pk[2];     // per layer: [2 dir][24 tiles][32 k-steps][64 lanes]
+  DevBuf<float> out_w, out_b;  // [V][256], [V]
+  DevBuf<float> zero_b;        // [V] zeros: the log_softmax kernel's bias in fp16 mode (the logits carry theirs)
+  DevBuf<__half> wih16[2];     // fp16 copies (precision 1)
+  DevBuf<__half> whh16_pk[2];  // per layer: [2 dir][24 tiles][8 k-steps][64 lanes][4]
+  DevBuf<__half> whh16x_pk[2]; // per layer: [2 dir][3 gates][8 waves][4 k-steps][64 lanes][8] (W_hh as 16x16x32 fragments, gate-scaled)
+  DevBuf<__half> wih16x_pk[2]; // per layer: [2 dir][3 gates][8 waves][din/32 k-steps][64 lanes][8] (fused-projection GRU, gate-scaled)
   bool gru_gemm;        // fp16 mode: input projections as a separate GEMM (WAKEWORD_CTC_GEMM=1; A/B and checks)
   // Decision-parity attribution (WAKEWORD_CTC_MIX): 1 = "out32", the fp16
   // path up to the last GRU layer, then the output layer in fp32 (y1 widened,
@@ -44,20 +47,20 @@ struct wk_ctc {
   // rounded to fp16).  0 (default) = the precision's own output layer.
   int mix;
   int rescore;          // fp16 output layer: near-tie rows re-decided in fp32 (default; WAKEWORD_CTC_RESCORE=0 off, A/B)
-  __half* out_w16;
-  float* fft_win;       // [400] periodic Hann
-  float* fft_tw;        // [20 k1][20 n2] W400^(n2 k1), complex
-  float* melw;          // ctc_logmel_fft2_kernel: per-lane padded mel weights x 1/4, [64][kMelW1] then [64][kMelW2]
-  int* melws;           // their window start bins, [64] then [64]
+  DevBuf<__half> out_w16;
+  DevBuf<float> fft_win;       // [400] periodic Hann
+  DevBuf<float> fft_tw;        // [20 k1][20 n2] W400^(n2 k1), complex
+  DevBuf<float> melw;          // ctc_logmel_fft2_kernel: per-lane padded mel weights x 1/4, [64][kMelW1] then [64][kMelW2]
+  DevBuf<int> melws;           // their window start bins, [64] then [64]
   // workspaces (grown on demand)
   size_t ws_rows;
-  float *x0, *gi, *y0, *y1, *logits;
-  __half *x0h, *y0h, *y1h, *logits16;
-  int* best;
-  int* best2;           // fp16 mode: the runner-up column of near-tie rows (else -1), for ctc_rescore_kernel
-  float* tr_feats;      // wk_ctc_transcribe: [rows][80] features (raw in fp16 mode), pass partials, per-utterance z-score
-  float2* tr_part;       // [tr_slots] per-wave log-mel statistics (ctc_logmel_fft2_kernel<true>)
-  float2* tr_zs;
+  DevBuf<float> x0, gi, y0, y1, logits;
+  DevBuf<__half> x0h, y0h, y1h, logits16;
+  DevBuf<int> best;
+  DevBuf<int> best2;           // fp16 mode: the runner-up column of near-tie rows (else -1), for ctc_rescore_kernel
+  DevBuf<float> tr_feats;      // wk_ctc_transcribe: [rows][80] features (raw in fp16 mode), pass partials, per-utterance z-score
+  DevBuf<float2> tr_part;      // [tr_slots] per-wave log-mel statistics (ctc_logmel_fft2_kernel<true>)
+  DevBuf<float2> tr_zs;
   size_t tr_rows, tr_batch, tr_slots;
   int64_t last_batch;   // geometry of the last wk_ctc_forward (wk_ctc_frame_argmax)
   int32_t last_T;
@@ -75,8 +78,9 @@ namespace {
 // wk_ctc_forward's workspace: which buffers this handle's path uses (fp32:
 // x0, gi, y0, y1, logits; fp16: the half tensors, gi only for the GEMM
 // projections; the attribution mixes add the other precision's y1 / logits).
+// It sizes and regrows them; the owners in the handle are what frees them.
 struct WsBuf {
-  void** p;
+  DevMem* buf;
   size_t row_bytes;
   bool needed;
 };
@@ -84,32 +88,33 @@ std::array<WsBuf, 11> ws_table(wk_ctc* c) {
   const bool f16 = c->f16;
   const size_t H = kH, V = (size_t)c->cfg.vocab;
   return {{
-      {(void**)&c->x0, sizeof(float) * H, !f16},
-      {(void**)&c->gi, sizeof(float) * 6 * H, !f16 || c->gru_gemm},
-      {(void**)&c->y0, sizeof(float) * 2 * H, !f16},
-      {(void**)&c->y1, sizeof(float) * 2 * H, !f16 || c->mix == 1},
-      {(void**)&c->logits, sizeof(float) * V, !f16 || c->mix == 1},
-      {(void**)&c->best, sizeof(int), true},
-      {(void**)&c->best2, sizeof(int), true},
-      {(void**)&c->x0h, sizeof(__half) * H, f16},
-      {(void**)&c->y0h, sizeof(__half) * 2 * H, f16},
-      {(void**)&c->y1h, sizeof(__half) * 2 * H, f16 || c->mix == 2},
-      {(void**)&c->logits16, sizeof(__half) * V, f16},
+      {&c->x0, sizeof(float) * H, !f16},
+      {&c->gi, sizeof(float) * 6 * H, !f16 || c->gru_gemm},
+      {&c->y0, sizeof(float) * 2 * H, !f16},
+      {&c->y1, sizeof(float) * 2 * H, !f16 || c->mix == 1},
+      {&c->logits, sizeof(float) * V, !f16 || c->mix == 1},
+      {&c->best, sizeof(int), true},
+      {&c->best2, sizeof(int), true},
+      {&c->x0h, sizeof(__half) * H, f16},
+      {&c->y0h, sizeof(__half) * 2 * H, f16},
+      {&c->y1h, sizeof(__half) * 2 * H, f16 || c->mix == 2},
+      {&c->logits16, sizeof(__half) * V, f16},
   }};
 }
 
-void free_ws(wk_ctc* c) {   // (the transcribe buffers go in free_all)
-  for (const WsBuf& b : ws_table(c)) {
-    (void)hipFree(*b.p);
-    *b.p = nullptr;
-  }
-  c->ws_rows = 0;
-}
-
+// Drops the old buffers first (two passes: the peak is the larger set alone);
+// nothing stays allocated after a failure.
 hipError_t alloc_ws(wk_ctc* c, size_t rows) {
+  c->ws_rows = 0;
+  for (const WsBuf& b : ws_table(c)) b.buf->reset();
   hipError_t e = hipSuccess;
   for (const WsBuf& b : ws_table(c))
-    if (b.needed && e == hipSuccess) e = hipMalloc(b.p, b.row_bytes * rows);
+    if (b.needed && e == hipSuccess) e = b.buf->alloc_bytes(b.row_bytes * rows);
+  if (e == hipSuccess) {
+    c->ws_rows = rows;
+  } else {
+    for (const WsBuf& b : ws_table(c)) b.buf->reset();
+  }
   return e;
 }
 
@@ -161,41 +166,12 @@ wk_status timed(wk_ctc* c, int stage, hipStream_t st, F body) {
   return s;
 }
 
-void free_tr(wk_ctc* c) {   // wk_ctc_transcribe's buffers
-  for (void** p : {(void**)&c->tr_feats, (void**)&c->tr_part, (void**)&c->tr_zs}) {
-    (void)hipFree(*p);
-    *p = nullptr;
-  }
-  c->tr_rows = c->tr_batch = c->tr_slots = 0;
-}
-
-void free_all(wk_ctc* c) {
-  (void)fold_events(c);
-  free_ws(c);
-  free_tr(c);
-  void* ps[] = {c->enc_w, c->enc_b, c->ln_g, c->ln_b, c->wih[0], c->wih[1], c->bih[0], c->bih[1], c->bhh[0],
-                c->bhh[1], c->whh_pk[0], c->whh_pk[1], c->out_w, c->out_b, c->zero_b, c->wih16[0], c->wih16[1],
-                c->out_w16, c->fft_win, c->fft_tw, c->whh16_pk[0], c->whh16_pk[1],
-                c->wih16x_pk[0], c->wih16x_pk[1], c->whh16x_pk[0], c->whh16x_pk[1], c->melw, c->melws};
-  for (void* q : ps) (void)hipFree(q);
-}
-
-template <typename T>
-hipError_t upload(T** d, const T* h, size_t n) {
-  hipError_t e = hipMalloc(d, sizeof(T) * n);
-  if (e != hipSuccess) return e;
-  return hipMemcpy(*d, h, sizeof(T) * n, hipMemcpyHostToDevice);
-}
-
-hipError_t upload_f16(__half** d, const float* h, size_t n) {
+hipError_t upload_f16(DevBuf<__half>& d, const float* h, size_t n) {
   std::vector<__half> t(n);
   for (size_t i = 0; i < n; ++i) t[i] = __float2half(h[i]);
-  return upload(d, t.data(), n);
+  return d.upload(t);
 }
-
-template <typename T>
-hipError_t upload(T** d, const std::vector<T>& h) { return upload(d, h.data(), h.size()); }
-hipError_t upload_f16(__half** d, const std::vector<float>& h) { return upload_f16(d, h.data(), h.size()); }
+hipError_t upload_f16(DevBuf<__half>& d, const std::vector<float>& h) { return upload_f16(d, h.data(), h.size()); }
 
 }  // namespace
 
@@ -216,7 +192,8 @@ wk_status wk_ctc_create(const wk_ctc_config* cfg, const float* w, wk_ctc** out) 
   if (cfg->precision != 0 && cfg->precision != 1) return invalid("wk_ctc_create: precision must be 0 (fp32) or 1 (fp16)");
   *out = nullptr;
   return on_device(cfg->device, [&]() -> wk_status {
-    wk_ctc* c = (wk_ctc*)calloc(1, sizeof(wk_ctc));
+    // (the scalar members start at zero; a failed create frees it here, device current)
+    std::unique_ptr<wk_ctc> c(new (std::nothrow) wk_ctc());
     if (!c) return WK_ERR_NO_MEMORY;
     c->cfg = *cfg;
     c->f16 = cfg->precision == 1;
@@ -231,10 +208,10 @@ wk_status wk_ctc_create(const wk_ctc_config* cfg, const float* w, wk_ctc** out) 
     const int H = kH, V = cfg->vocab;
     const float* p = w;
     auto take = [&](size_t n) { const float* q = p; p += n; return q; };
-    hipError_t e = upload(&c->enc_w, take((size_t)H * kMels), (size_t)H * kMels);
-    if (e == hipSuccess) e = upload(&c->enc_b, take(H), H);
-    if (e == hipSuccess) e = upload(&c->ln_g, take(H), H);
-    if (e == hipSuccess) e = upload(&c->ln_b, take(H), H);
+    hipError_t e = c->enc_w.upload(take((size_t)H * kMels), (size_t)H * kMels);
+    if (e == hipSuccess) e = c->enc_b.upload(take(H), H);
+    if (e == hipSuccess) e = c->ln_g.upload(take(H), H);
+    if (e == hipSuccess) e = c->ln_b.upload(take(H), H);
     for (int l = 0; l < 2 && e == hipSuccess; ++l) {
       // the blob holds, per direction, W_ih, W_hh, b_ih, b_hh; the kernels take each tensor with both directions adjacent
       const int din = l == 0 ? H : 2 * H;
@@ -245,32 +222,28 @@ wk_status wk_ctc_create(const wk_ctc_config* cfg, const float* w, wk_ctc** out) 
         memcpy(&bih[d * 3 * H], take(3 * H), sizeof(float) * 3 * H);
         memcpy(&bhh[d * 3 * H], take(3 * H), sizeof(float) * 3 * H);
       }
-      e = upload(&c->wih[l], wih);
-      if (e == hipSuccess && c->f16) e = upload_f16(&c->wih16[l], wih);
-      if (e == hipSuccess && c->f16) e = upload_f16(&c->wih16x_pk[l], ctc_pack_frag32(wih.data(), din, kCtcGateScale));
-      if (e == hipSuccess && c->f16) e = upload_f16(&c->whh16x_pk[l], ctc_pack_frag32(whh.data(), H, kCtcGateScale));
-      if (e == hipSuccess) e = upload(&c->bih[l], bih);
-      if (e == hipSuccess) e = upload(&c->bhh[l], bhh);
-      if (e == hipSuccess) e = upload(&c->whh_pk[l], ctc_pack_whh(whh.data()));
-      if (e == hipSuccess && c->f16) e = upload_f16(&c->whh16_pk[l], ctc_pack_whh16(whh.data()));
+      e = c->wih[l].upload(wih);
+      if (e == hipSuccess && c->f16) e = upload_f16(c->wih16[l], wih);
+      if (e == hipSuccess && c->f16) e = upload_f16(c->wih16x_pk[l], ctc_pack_frag32(wih.data(), din, kCtcGateScale));
+      if (e == hipSuccess && c->f16) e = upload_f16(c->whh16x_pk[l], ctc_pack_frag32(whh.data(), H, kCtcGateScale));
+      if (e == hipSuccess) e = c->bih[l].upload(bih);
+      if (e == hipSuccess) e = c->bhh[l].upload(bhh);
+      if (e == hipSuccess) e = c->whh_pk[l].upload(ctc_pack_whh(whh.data()));
+      if (e == hipSuccess && c->f16) e = upload_f16(c->whh16_pk[l], ctc_pack_whh16(whh.data()));
     }
     const float* ow = take((size_t)V * 2 * H);
-    if (e == hipSuccess) e = upload(&c->out_w, ow, (size_t)V * 2 * H);
-    if (e == hipSuccess && (c->f16 || c->mix == 2)) e = upload_f16(&c->out_w16, ow, (size_t)V * 2 * H);
-    if (e == hipSuccess) e = upload(&c->out_b, take(V), V);
-    if (e == hipSuccess) e = upload(&c->zero_b, std::vector<float>((size_t)V, 0.0f));
+    if (e == hipSuccess) e = c->out_w.upload(ow, (size_t)V * 2 * H);
+    if (e == hipSuccess && (c->f16 || c->mix == 2)) e = upload_f16(c->out_w16, ow, (size_t)V * 2 * H);
+    if (e == hipSuccess) e = c->out_b.upload(take(V), V);
+    if (e == hipSuccess) e = c->zero_b.upload(std::vector<float>((size_t)V, 0.0f));
     CtcLogmelTables lm;
     if (e == hipSuccess && !ctc_logmel_tables(&lm)) e = hipErrorInvalidValue;
-    if (e == hipSuccess) e = upload(&c->fft_win, lm.win);
-    if (e == hipSuccess) e = upload(&c->fft_tw, lm.tw);
-    if (e == hipSuccess) e = upload(&c->melw, lm.melw);
-    if (e == hipSuccess) e = upload(&c->melws, lm.melws);
-    if (e != hipSuccess) {
-      free_all(c);
-      free(c);
-      return e == hipErrorOutOfMemory ? WK_ERR_NO_MEMORY : hip_fail(e, "wk_ctc_create");
-    }
-    *out = c;
+    if (e == hipSuccess) e = c->fft_win.upload(lm.win);
+    if (e == hipSuccess) e = c->fft_tw.upload(lm.tw);
+    if (e == hipSuccess) e = c->melw.upload(lm.melw);
+    if (e == hipSuccess) e = c->melws.upload(lm.melws);
+    if (e != hipSuccess) return e == hipErrorOutOfMemory ? WK_ERR_NO_MEMORY : hip_fail(e, "wk_ctc_create");
+    *out = c.release();
     return WK_OK;
   });
 }
@@ -279,8 +252,8 @@ wk_status wk_ctc_destroy(wk_ctc* c) {
   if (!c) return WK_OK;
   return on_device(c->cfg.device, [&]() -> wk_status {
     (void)hipDeviceSynchronize();
-    free_all(c);
-    free(c);
+    (void)fold_events(c);   // (destroys the stage events still recorded)
+    delete c;
     return WK_OK;
   });
 }
@@ -379,7 +352,7 @@ wk_status stage_out32(const Fwd& f, const float* y, float* d_log_probs) {
   const int V = c->cfg.vocab;
   return timed(c, WK_CTC_STAGE_OUTPUT, f.st, [&]() -> wk_status {
     if (!d_log_probs)   // decode only: the argmax inside the GEMM, no [rows][V] logits (c->logits: the keys)
-      return ctc_gemm_argmax(f.st, f.rows, V, 2 * kH, y, c->out_w, c->out_b, reinterpret_cast<unsigned long long*>(c->logits),
+      return ctc_gemm_argmax(f.st, f.rows, V, 2 * kH, y, c->out_w, c->out_b, reinterpret_cast<unsigned long long*>(c->logits.get()),
                              c->best);
     const wk_status g = ctc_gemm_nt(f.st, f.rows, V, 2 * kH, y, c->out_w, c->logits, false);
     if (g != WK_OK) return g;
@@ -410,12 +383,8 @@ wk_status ctc_forward(wk_ctc* c, const float* d_feats, int64_t batch, int32_t T,
     hipError_t e;
     if ((size_t)rows > c->ws_rows) {   // workspace grows on first use of a larger batch (then reused)
       if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(e, "sync");
-      free_ws(c);
-      if ((e = alloc_ws(c, (size_t)rows)) != hipSuccess) {
-        free_ws(c);
+      if ((e = alloc_ws(c, (size_t)rows)) != hipSuccess)
         return e == hipErrorOutOfMemory ? WK_ERR_NO_MEMORY : hip_fail(e, "wk_ctc_forward workspace");
-      }
-      c->ws_rows = rows;
     }
     c->last_batch = batch;
     c->last_T = T;
@@ -467,10 +436,12 @@ wk_status wk_ctc_transcribe(wk_ctc* c, const float* d_audio, int64_t batch, int3
     const int64_t slots = ctc_logmel_layout(c->n_cu, rows, T).slots;
     if ((size_t)rows > c->tr_rows || (size_t)batch > c->tr_batch || (size_t)slots > c->tr_slots) {   // grows, then reused
       if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(e, "sync");
-      free_tr(c);
-      if ((e = hipMalloc(&c->tr_feats, sizeof(float) * rows * kMels)) != hipSuccess ||
-          (e = hipMalloc(&c->tr_part, sizeof(float2) * slots)) != hipSuccess ||
-          (e = hipMalloc(&c->tr_zs, sizeof(float2) * batch)) != hipSuccess)
+      c->tr_rows = c->tr_batch = c->tr_slots = 0;
+      c->tr_feats.reset();   // (all three go before any grows: the peak is the larger set alone)
+      c->tr_part.reset();
+      c->tr_zs.reset();
+      if ((e = c->tr_feats.alloc((size_t)rows * kMels)) != hipSuccess || (e = c->tr_part.alloc((size_t)slots)) != hipSuccess ||
+          (e = c->tr_zs.alloc((size_t)batch)) != hipSuccess)
         return e == hipErrorOutOfMemory ? WK_ERR_NO_MEMORY : hip_fail(e, "wk_ctc_transcribe workspace");
       c->tr_rows = (size_t)rows;
       c->tr_batch = (size_t)batch;

@@ -31,22 +31,24 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <memory>
 #include <mutex>
 #include <new>
 #include <vector>
 
+#include "wk_devmem.h"
 #include "wk_esp_tables.h"
 #include "wk_kernels.h"
 
 struct wk_esp_mfcc {
   int32_t sr, frame, n_fft, n_filters, n_mfcc, esp_pack, device, log2n;
-  float* d_win = nullptr;     // [frame] symmetric Hamming (mfcc.c:118-120)
-  float2* d_tw = nullptr;     // [n_fft / 2] W^k = exp(-2 pi i k / n_fft)
-  int2* d_rows = nullptr;     // [n_filters] {first weight index, first bin} ...
-  int* d_rlen = nullptr;      // [n_filters] ... and the row's length
-  float* d_fbw = nullptr;     // the rows' weights, back to back
-  float* d_dct = nullptr;     // [min(n_mfcc, n_filters)][n_filters] cosines
-  float* d_scale = nullptr;   // [min(n_mfcc, n_filters)] sqrt(1/n), sqrt(2/n)
+  wk::DevBuf<float> d_win;     // [frame] symmetric Hamming (mfcc.c:118-120)
+  wk::DevBuf<float2> d_tw;     // [n_fft / 2] W^k = exp(-2 pi i k / n_fft)
+  wk::DevBuf<int2> d_rows;     // [n_filters] {first weight index, first bin} ...
+  wk::DevBuf<int> d_rlen;      // [n_filters] ... and the row's length
+  wk::DevBuf<float> d_fbw;     // the rows' weights, back to back (may be empty: still one element)
+  wk::DevBuf<float> d_dct;     // [min(n_mfcc, n_filters)][n_filters] cosines
+  wk::DevBuf<float> d_scale;   // [min(n_mfcc, n_filters)] sqrt(1/n), sqrt(2/n)
 };
 
 namespace {
@@ -133,19 +135,6 @@ __global__ __launch_bounds__(kEspBlock) void wk_esp_mfcc_kernel(
   }
 }
 
-template <typename T>
-hipError_t upload(T** d, const std::vector<T>& h) {
-  hipError_t e = hipMalloc(d, sizeof(T) * (h.empty() ? 1 : h.size()));
-  if (e != hipSuccess) return e;
-  return h.empty() ? hipSuccess : hipMemcpy(*d, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice);
-}
-
-void free_tables(wk_esp_mfcc* m) {
-  for (void* p : {(void*)m->d_win, (void*)m->d_tw, (void*)m->d_rows, (void*)m->d_rlen, (void*)m->d_fbw, (void*)m->d_dct,
-                  (void*)m->d_scale})
-    if (p) (void)hipFree(p);
-}
-
 }  // namespace
 
 using wk::hip_fail;
@@ -161,9 +150,6 @@ wk_status wk_esp_mfcc_create(int32_t sampling_rate, int32_t frame_size, int32_t 
   if (lg < 0)
     return invalid("wk_esp_mfcc_create: parameters outside mfcc.c's domain (n_fft a power of 2 in [2, 4096], "
                    "1 <= n_filters <= 1024, frame_size, n_mfcc, sampling_rate >= 1)");
-  wk_esp_mfcc* m = new (std::nothrow) wk_esp_mfcc;
-  if (!m) return WK_ERR_NO_MEMORY;
-  *m = wk_esp_mfcc{sampling_rate, frame_size, n_fft, n_filters, n_mfcc, esp_dsp_packing ? 1 : 0, device, lg};
   // window (mfcc.c:118-120: alpha - (1 - alpha) cos(2 pi i / (frame - 1)), float, the angle in double)
   const std::vector<float> win = wk::esp::window(frame_size);
   std::vector<float2> tw(n_fft / 2);
@@ -190,25 +176,19 @@ wk_status wk_esp_mfcc_create(int32_t sampling_rate, int32_t frame_size, int32_t 
   // DCT-II cosines (mfcc.c:26-30 / :44-48: cos of the float-converted double angle) and scales (:33, :57)
   std::vector<float> dct, scale;
   wk::esp::dct(n_mfcc, n_filters, dct, scale);
-  const wk_status s = wk::on_device(device, [&]() -> wk_status {
+  return wk::on_device(device, [&]() -> wk_status {
+    std::unique_ptr<wk_esp_mfcc> m(new (std::nothrow) wk_esp_mfcc{   // (a failed create frees it here, device current)
+        sampling_rate, frame_size, n_fft, n_filters, n_mfcc, esp_dsp_packing ? 1 : 0, device, lg});
+    if (!m) return WK_ERR_NO_MEMORY;
     hipError_t e;
-    if ((e = upload(&m->d_win, win)) != hipSuccess || (e = upload(&m->d_tw, tw)) != hipSuccess ||
-        (e = upload(&m->d_rows, rows)) != hipSuccess || (e = upload(&m->d_rlen, rlen)) != hipSuccess ||
-        (e = upload(&m->d_fbw, fbw)) != hipSuccess || (e = upload(&m->d_dct, dct)) != hipSuccess ||
-        (e = upload(&m->d_scale, scale)) != hipSuccess)
+    if ((e = m->d_win.upload(win)) != hipSuccess || (e = m->d_tw.upload(tw)) != hipSuccess ||
+        (e = m->d_rows.upload(rows)) != hipSuccess || (e = m->d_rlen.upload(rlen)) != hipSuccess ||
+        (e = m->d_fbw.upload(fbw)) != hipSuccess || (e = m->d_dct.upload(dct)) != hipSuccess ||
+        (e = m->d_scale.upload(scale)) != hipSuccess)
       return hip_fail(e, "wk_esp_mfcc_create: table upload");
+    *out = m.release();
     return WK_OK;
   });
-  if (s != WK_OK) {
-    (void)wk::on_device(device, [&]() -> wk_status {
-      free_tables(m);
-      return WK_OK;
-    });
-    delete m;
-    return s;
-  }
-  *out = m;
-  return WK_OK;
 }
 
 wk_status wk_esp_mfcc_run(wk_esp_mfcc* m, const float* d_signal, int64_t batch, int32_t signal_len, int64_t stride,
@@ -236,11 +216,11 @@ wk_status wk_esp_mfcc_run(wk_esp_mfcc* m, const float* d_signal, int64_t batch, 
 
 wk_status wk_esp_mfcc_destroy(wk_esp_mfcc* m) {
   if (!m) return WK_OK;
-  (void)wk::on_device(m->device, [&]() -> wk_status {
-    free_tables(m);
+  const wk_status s = wk::on_device(m->device, [&]() -> wk_status {
+    delete m;
     return WK_OK;
   });
-  delete m;
+  if (s != WK_OK) delete m;   // the device could not be made current: the object goes all the same
   return WK_OK;
 }
 

@@ -34,6 +34,7 @@
 
 #include "wakeword_host.h"
 #include "wk_esp_tables.h"
+#include "wk_mfcc_shim.h"
 #include "wk_status.h"
 
 // The error helpers of wk_status.h for this library (wk_wav.cpp reports through them too).
@@ -556,19 +557,12 @@ const char* wkh_last_error(void) { return wk::g_last_error.c_str(); }
 // ---------------------------------------------------------------------------
 float* extract_mfcc(const float* signal, int signal_len, int sampling_rate, int frame_size, int hop_size, int n_fft,
                     int n_filters, int n_mfcc) {
-  if (!signal || signal_len < frame_size || frame_size <= 0) {   // mfcc.c:434-437
-    fprintf(stderr, "E (MFCC) Invalid signal parameters\n");
-    return nullptr;
-  }
-  if (hop_size < 1) {   // (mfcc.c:447 divides by it)
-    fprintf(stderr, "E (MFCC) Invalid hop size\n");
-    return nullptr;
-  }
+  if (!wk::shim::check_signal(signal, signal_len, frame_size, hop_size)) return nullptr;
   if (wk::esp::check_domain(sampling_rate, frame_size, n_fft, n_filters, n_mfcc) < 0) {
     fprintf(stderr, "E (MFCC) unsupported configuration\n");
     return nullptr;
   }
-  const int nf = (signal_len - frame_size) / hop_size + 1;
+  const int nf = wk::shim::frame_count(signal_len, frame_size, hop_size);
   float* out = (float*)malloc(sizeof(float) * (size_t)nf * n_mfcc);
   if (!out) {
     fprintf(stderr, "E (MFCC) Memory allocation failed\n");
@@ -588,10 +582,7 @@ void free_mfcc(float* mfcc) { free(mfcc); }
 // mfcc.c:297-427: one frame, no pre-emphasis -> malloc'd n_mfcc floats.
 float* flow_extract_mfcc_single_frame(const float* frame, int frame_size, int sampling_rate, int n_fft, int n_filters,
                                       int n_mfcc) {
-  if (!frame || frame_size <= 0 || frame_size > n_fft) {   // mfcc.c:300-303
-    fprintf(stderr, "E (MFCC) Invalid frame parameters\n");
-    return nullptr;
-  }
+  if (!wk::shim::check_frame(frame, frame_size, n_fft)) return nullptr;
   if (n_mfcc < 1 || wk::esp::check_domain(sampling_rate, frame_size, n_fft, n_filters, n_mfcc) < 0) {
     fprintf(stderr, "E (MFCC) unsupported configuration\n");
     return nullptr;
@@ -606,25 +597,6 @@ float* flow_extract_mfcc_single_frame(const float* frame, int frame_size, int sa
   return out;
 }
 
-// mfcc.c:530-553: min/max/avg over the finite entries.
-void analyze_mfcc_range(float* mfcc, int size, const char* label) {
-  if (!mfcc || size <= 0) return;
-  float mn = INFINITY, mx = -INFINITY, sum = 0.0f;
-  int valid = 0;
-  for (int i = 0; i < size; i++) {
-    if (!isnan(mfcc[i]) && !isinf(mfcc[i])) {
-      mn = std::min(mn, mfcc[i]);
-      mx = std::max(mx, mfcc[i]);
-      sum += mfcc[i];
-      valid++;
-    }
-  }
-  if (valid > 0)
-    printf("I (MFCC) %s MFCC Range: min=%.6f, max=%.6f, avg=%.6f, valid=%d/%d\n", label ? label : "", mn, mx,
-           sum / valid, valid, size);
-  else
-    fprintf(stderr, "E (MFCC) %s MFCC: No valid values\n", label ? label : "");
-  fflush(stdout);
-}
+void analyze_mfcc_range(float* mfcc, int size, const char* label) { wk::shim::analyze_range(mfcc, size, label); }
 
 }  // extern "C"

@@ -12,7 +12,7 @@
 
 namespace wk {
 
-// Error reporting shared by the C-ABI translation units (wk_api.hip, wk_ctc.hip;
+// Error reporting shared by the C-ABI translation units (defined in wk_api.hip;
 // g_last_error, invalid and fail in wk_status.h).
 wk_status hip_fail(hipError_t e, const char* what);
 
@@ -33,21 +33,6 @@ wk_status on_device(int dev, F body) {
 hipError_t launch_frontend(bool mode_b, bool i16, const void* audio, int64_t batch, int win_len,
                            int64_t clip_stride, float* out, int esp_pack, int cmvn, int grid_cap,
                            float pre_emphasis, hipStream_t stream);   // pre_emphasis: 0.97 (mfcc.c:445), 0 = none
-
-// Shared-frame scan (wk_scan.hip), mode B, hop = 256k with k <= kScanMaxK.
-// launch_scan_frames: raw MFCC of global frames 1..G of each of n_rec
-// recordings -> store [n_rec][13][g_pad], frame g at column g (g_pad > G).
-// launch_scan_assemble: units [unit0, unit0 + n_units) of <= wpu (<= kScanUnitWindows)
-// consecutive windows of one recording each, ceil(W / wpu) units per recording:
-// edge frames 0 and 62 of every window + frames 1..61 from the store + CMVN ->
-// feats + (flat window index - flat0) * 819, flat index = rec * W + w.
-constexpr int kScanMaxK = 61;          // beyond it consecutive windows share no interior frame
-constexpr int kScanUnitWindows = 31;   // 62 edge frames per work unit
-hipError_t launch_scan_frames(bool i16, const void* audio, int64_t n_rec, int64_t rec_stride, int G, int g_pad,
-                              float* store, int grid_cap, hipStream_t stream);
-hipError_t launch_scan_assemble(bool i16, const void* audio, int64_t rec_stride, int hop, int64_t W, int wpu,
-                                int64_t unit0, int64_t n_units, int64_t flat0, int g_pad, const float* store,
-                                float* feats, int grid_cap, hipStream_t stream);
 
 // Fused front-end + CNN (wk_fused.hip), mode B only.
 // w = fp32 fragment-major weights (pack_fragments); wbf = bf16 conv fragments
@@ -85,16 +70,6 @@ hipError_t launch_int8_cnn(const float* feats, int64_t batch, const int8_t* wq, 
                            int grid_cap, hipStream_t stream);
 void quantize_int8_weights(const float* w, const int32_t* e_w, int8_t* q);
 
-// Calibration (wk_quant.hip).  Workspace: the 64-bit totals ([7][32] counts, then the 7 maxima as bit
-// patterns of |x|), fragment-major forward weights, then one slot of kCalibSlot 32-bit words per workgroup
-// (7 x 32 counts, 7 maxima).  Workgroup g walks clips g, g + grid, ...; grid = min(batch, kCalibGridCap).
-constexpr int kCalibTotals = WK_QUANT_TENSORS * WK_QUANT_BINS + WK_QUANT_TENSORS;
-constexpr int kCalibSlot = WK_QUANT_TENSORS * WK_QUANT_BINS + 8;
-constexpr int kCalibGridCap = 512;
-constexpr size_t kCalibTotalsBytes = (kCalibTotals * 8 + 255) & ~(size_t)255;
-size_t calibrate_workspace_bytes(int64_t batch);
-// Queues the pack, count and sum kernels; the totals are at the start of the workspace afterwards.
-hipError_t launch_calibrate(const float* w, const float* feats, int64_t batch, void* workspace, hipStream_t stream);
 // Time steps of the input and after each of the three pools (the widths the direct-form tiles of wk_direct_dev.h
 // are cut to), and with them the values per clip of the seven tensors calibration observes.
 constexpr int kConvSteps[4] = {63, 31, 15, 7};
@@ -112,8 +87,6 @@ hipError_t launch_normalize(const float* in, float* out, int64_t batch, int n_co
 // The firmware's per-window CMVN over an MFCC frame stream (wk_device_cmvn).
 hipError_t launch_record_front(const int16_t* tdm, int64_t n_out, int16_t* out16, float* outf, hipStream_t stream);
 hipError_t launch_quantize_frames(const float* x, int64_t n, int8_t* q, hipStream_t stream);
-// wk_stream_push: ring samples [pos, pos + m) mod cap, host staging ring -> mirrored device ring.
-hipError_t launch_ring_ingest(const float* src, float* dst, int64_t cap, int64_t pos, int64_t m, hipStream_t stream);
 hipError_t launch_device_cmvn(const void* frames, bool int8_in, int64_t n_windows, int8_t* out_i8, float* out_f,
                               hipStream_t stream);
 

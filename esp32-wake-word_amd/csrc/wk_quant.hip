@@ -31,13 +31,28 @@
 // Each workgroup writes its counters once to its own slot of the workspace;
 // wk_calib_sum_kernel adds the slots into 64-bit totals.  No floating-point
 // atomics and no global atomics: integer sums, identical between calls.
+//
+// The C entry points of the int8 spec (wk_quant_spec_default, wk_set_quant,
+// wk_get_quant, wk_quant_weights) and of calibration, with its host step (the
+// percentile read off the totals), are at the end of this file.
+#include <math.h>
+
 #include "wk_direct_dev.h"
+#include "wk_handle.h"
 #include "wk_quant_rule.h"
 
 namespace wk {
 namespace {
 
 constexpr int kNT = WK_QUANT_TENSORS, kNB = WK_QUANT_BINS;
+
+// Workspace: the 64-bit totals ([7][32] counts, then the 7 maxima as bit patterns of |x|), fragment-major
+// forward weights, then one slot of kCalibSlot 32-bit words per workgroup (7 x 32 counts, 7 maxima).
+// Workgroup g walks clips g, g + grid, ...; grid = min(batch, kCalibGridCap).
+constexpr int kCalibTotals = kNT * kNB + kNT;
+constexpr int kCalibSlot = kNT * kNB + 8;
+constexpr int kCalibGridCap = 512;
+constexpr size_t kCalibTotalsBytes = (kCalibTotals * 8 + 255) & ~(size_t)255;
 
 // Count one value per lane into the tensor's 32 LDS counters; idx < 0: this
 // lane has no value.  Every lane of the wave must call it together.
@@ -153,13 +168,12 @@ __global__ void wk_calib_sum_kernel(const unsigned* __restrict__ slots, int nslo
   tot[i] = v;
 }
 
-}  // namespace
-
 size_t calibrate_workspace_bytes(int64_t batch) {
   const int64_t grid = batch < kCalibGridCap ? batch : kCalibGridCap;
   return kCalibTotalsBytes + sizeof(float) * kDirectFwdPacked + sizeof(uint32_t) * kCalibSlot * (size_t)grid;
 }
 
+// Queues the pack, count and sum kernels; the totals are at the start of the workspace afterwards.
 hipError_t launch_calibrate(const float* w, const float* feats, int64_t batch, void* workspace, hipStream_t stream) {
   unsigned long long* tot = (unsigned long long*)workspace;
   float* pk = (float*)((char*)workspace + kCalibTotalsBytes);
@@ -172,4 +186,117 @@ hipError_t launch_calibrate(const float* w, const float* feats, int64_t batch, v
   return hipGetLastError();
 }
 
+}  // namespace
 }  // namespace wk
+
+using wk::hip_fail;
+using wk::invalid;
+using wk::on_device;
+
+// ---------------------------------------------------------------------------
+// Post-training int8 quantisation: the spec, and calibration's host step.
+// ---------------------------------------------------------------------------
+extern "C" {
+
+wk_status wk_quant_spec_default(wk_quant_spec* out) {
+  if (!out) return invalid("wk_quant_spec_default: null out");
+  *out = wk_quant_spec{-4, {-8, -9, -9, -9, -9}, {-5, -5, -4, -5, -4, -3}};
+  return WK_OK;
+}
+
+wk_status wk_set_quant(wk_handle* h, const wk_quant_spec* spec) {
+  if (!spec) return invalid("wk_set_quant: null spec");
+  wk::Int8Params p;
+  if (const char* why = wk::int8_params(*spec, &p)) return invalid(why);
+  if (!h) return invalid("wk_set_quant: null handle");
+  if (h->cfg.precision != WK_PREC_INT8 || !h->d_int8) return invalid("wk_set_quant: not a WK_PREC_INT8 handle with weights");
+  std::vector<int8_t> q(wk::kNumInt8Weights);
+  wk::quantize_int8_weights(h->h_w.data(), spec->e_w, q.data());
+  return on_device(h->cfg.device, [&]() -> wk_status {
+    // launches already queued (on any stream) still read the old bytes: drain them first
+    hipError_t e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "wk_set_quant: sync");
+    if ((e = hipMemcpy(h->d_int8, q.data(), q.size(), hipMemcpyHostToDevice)) != hipSuccess)
+      return hip_fail(e, "wk_set_quant: hipMemcpy(int8 weights)");
+    h->quant = *spec;
+    h->qp = p;
+    return WK_OK;
+  });
+}
+
+wk_status wk_get_quant(wk_handle* h, wk_quant_spec* out) {
+  if (!h || !out) return invalid("wk_get_quant: null argument");
+  if (h->cfg.precision != WK_PREC_INT8) return invalid("wk_get_quant: not a WK_PREC_INT8 handle");
+  *out = h->quant;
+  return WK_OK;
+}
+
+wk_status wk_quant_weights(const float* host_weights, const wk_quant_spec* spec, int8_t* out) {
+  if (!host_weights || !spec || !out) return invalid("wk_quant_weights: null argument");
+  for (int i = 0; i < 5; ++i)
+    if (spec->e_w[i] < -32 || spec->e_w[i] > 32) return invalid("wk_quant_weights: weight exponent outside [-32, 32]");
+  wk::quantize_int8_weights(host_weights, spec->e_w, out);
+  return WK_OK;
+}
+
+wk_status wk_calibrate_workspace_bytes(int64_t batch, size_t* bytes) {
+  if (!bytes) return invalid("wk_calibrate_workspace_bytes: null bytes");
+  *bytes = 0;
+  if (batch < 1) return invalid("wk_calibrate_workspace_bytes: batch < 1");
+  *bytes = wk::calibrate_workspace_bytes(batch);
+  return WK_OK;
+}
+
+wk_status wk_calibrate(wk_handle* h, const float* d_feats, int64_t batch, double percentile, int32_t pin_e_in,
+                       void* d_workspace, size_t workspace_bytes, wk_quant_spec* out, wk_calib_stats* stats_or_null,
+                       void* stream) {
+  if (!h) return invalid("wk_calibrate: null handle");
+  if (!h->d_weights) return invalid("wk_calibrate: handle created without weights");
+  if (!d_feats || !out || batch < 1) return invalid("wk_calibrate: null pointer or batch < 1");
+  if (!(percentile > 0.0)) return invalid("wk_calibrate: percentile must be > 0");
+  if (pin_e_in != WK_QUANT_CALIBRATE_INPUT && (pin_e_in < -32 || pin_e_in > 32))
+    return invalid("wk_calibrate: pinned input exponent outside [-32, 32]");
+  if (!d_workspace || ((uintptr_t)d_workspace & 255) || workspace_bytes < wk::calibrate_workspace_bytes(batch))
+    return invalid("wk_calibrate: workspace null, not 256-byte aligned or below wk_calibrate_workspace_bytes");
+  unsigned long long tot[wk::kCalibTotals];
+  const wk_status st = on_device(h->cfg.device, [&]() -> wk_status {
+    const hipStream_t s = (hipStream_t)stream;
+    hipError_t e = wk::launch_calibrate(h->d_weights, d_feats, batch, d_workspace, s);
+    if (e != hipSuccess) return hip_fail(e, "calibrate launch");
+    if ((e = hipMemcpyAsync(tot, d_workspace, sizeof(tot), hipMemcpyDeviceToHost, s)) != hipSuccess ||
+        (e = hipStreamSynchronize(s)) != hipSuccess)
+      return hip_fail(e, "wk_calibrate: read back");
+    return WK_OK;
+  });
+  if (st != WK_OK) return st;
+  int e_t[WK_QUANT_TENSORS];
+  for (int t = 0; t < WK_QUANT_TENSORS; ++t) {
+    const unsigned long long* c = tot + t * WK_QUANT_BINS;
+    const int64_t n = wk::kCalibPerClip[t] * batch;
+    // the smallest bin whose cumulative count reaches k = ceil(percentile / 100 * n); >= 100: the maximum's bin
+    int64_t k = percentile >= 100.0 ? n : (int64_t)ceil(percentile / 100.0 * (double)n);
+    k = k < 1 ? 1 : (k > n ? n : k);
+    int64_t cum = 0;
+    int b = 0;
+    for (; b < WK_QUANT_BINS - 1; ++b)
+      if ((cum += (int64_t)c[b]) >= k) break;
+    e_t[t] = b - 24;
+    if (stats_or_null) {
+      for (int i = 0; i < WK_QUANT_BINS; ++i) stats_or_null->counts[t][i] = (int64_t)c[i];
+      const uint32_t mb = (uint32_t)tot[WK_QUANT_TENSORS * WK_QUANT_BINS + t];
+      memcpy(&stats_or_null->max_abs[t], &mb, 4);
+    }
+  }
+  if (stats_or_null) stats_or_null->n_clips = batch;
+  out->e_in = pin_e_in != WK_QUANT_CALIBRATE_INPUT ? pin_e_in : e_t[0];
+  for (int i = 0; i < 6; ++i) out->e_act[i] = e_t[1 + i];
+  static const int off[6] = {wk::kOffW1, wk::kOffW2, wk::kOffW3, wk::kOffF1, wk::kOffF2, wk::kNumWeights};
+  for (int i = 0; i < 5; ++i) {
+    float m = 0.0f;
+    for (int j = off[i]; j < off[i + 1]; ++j) m = fmaxf(m, fabsf(h->h_w[j]));
+    out->e_w[i] = wk::hold_exp(m);
+  }
+  return WK_OK;
+}
+
+}  // extern "C"

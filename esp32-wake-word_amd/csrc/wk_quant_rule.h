@@ -1,5 +1,5 @@
-// wk_quant_rule.h -- the power-of-2 quantiser's exponent rule, for the host (weight exponents, wk_api.hip) and
-// the device (activation bins, wk_quant.hip).
+// wk_quant_rule.h -- the power-of-2 quantiser's exponent rule, for the host (weight exponents, wk_calibrate) and
+// the device (activation bins), both in wk_quant.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -21,8 +21,9 @@
 //       2 edge frames of each window through the GENERAL (reflecting) loader,
 //       then per window one wave gathers frames 1..61 from the frame store,
 //       applies CMVN across the 63 lanes and writes the [13][63] features.
-// The CNN then runs on each chunk of features (wk_api.hip wk_scan).
-#include "wk_kernels.h"
+// The CNN then runs on each chunk of features (wk_scan below, which plans the
+// chunks; wk_scan_workspace_bytes sizes the frame store and the chunk buffer).
+#include "wk_handle.h"
 
 using namespace wk;
 
@@ -200,9 +201,15 @@ __global__ __launch_bounds__(kFeBlock, 4) void wk_scan_assemble_kernel(const T* 
   }
 }
 
-}  // namespace
-
-namespace wk {
+// Launchers, mode B, hop = 256k with k <= kScanMaxK.
+// launch_scan_frames: raw MFCC of global frames 1..G of each of n_rec
+// recordings -> store [n_rec][13][g_pad], frame g at column g (g_pad > G).
+// launch_scan_assemble: units [unit0, unit0 + n_units) of <= wpu (<= kScanUnitWindows)
+// consecutive windows of one recording each, ceil(W / wpu) units per recording:
+// edge frames 0 and 62 of every window + frames 1..61 from the store + CMVN ->
+// feats + (flat window index - flat0) * 819, flat index = rec * W + w.
+constexpr int kScanMaxK = 61;          // beyond it consecutive windows share no interior frame
+constexpr int kScanUnitWindows = 31;   // 62 edge frames per work unit
 
 hipError_t launch_scan_frames(bool i16, const void* audio, int64_t n_rec, int64_t rec_stride, int G, int g_pad,
                               float* store, int grid_cap, hipStream_t stream) {
@@ -235,4 +242,120 @@ hipError_t launch_scan_assemble(bool i16, const void* audio, int64_t rec_stride,
   return hipGetLastError();
 }
 
-}  // namespace wk
+// ---------------------------------------------------------------------------
+// wk_scan: every window [w*hop, w*hop + 16000) of long recordings.
+// ---------------------------------------------------------------------------
+constexpr int64_t kScanMaxSamples = (int64_t)1 << 30;
+constexpr int64_t kScanChunkWindows = 65536;                  // default windows per chunk (215 MB of features)
+constexpr size_t kScanFeatBytes = sizeof(float) * 13 * 63;    // 3276 B of features per window
+
+struct ScanPlan {
+  int64_t W;           // windows per recording
+  bool shared;         // hop = 256k, k <= kScanMaxK: interior frames computed once per recording
+  int k;
+  int G, g_pad;        // global frames 1..G; frame-store pitch (column g, a multiple of 64 above G)
+  size_t store_bytes;  // frame store [n_rec][13][g_pad], rounded up to 256 B
+};
+
+ScanPlan scan_plan(int64_t n_rec, int64_t n_samples, int32_t hop) {
+  ScanPlan p = {};
+  p.W = n_samples < WK_WIN_SAMPLES ? 0 : (n_samples - WK_WIN_SAMPLES) / hop + 1;
+  p.shared = p.W > 0 && n_rec > 0 && hop % 256 == 0 && hop / 256 <= kScanMaxK;
+  if (p.shared) {
+    p.k = hop / 256;
+    p.G = (int)(p.k * (p.W - 1) + 61);
+    p.g_pad = (p.G + 1 + 63) & ~63;
+    p.store_bytes = ((size_t)n_rec * 13 * p.g_pad * sizeof(float) + 255) & ~(size_t)255;
+  }
+  return p;
+}
+
+wk_status scan_check_geometry(int64_t n_rec, int64_t n_samples, int32_t hop) {
+  if (hop < 1) return invalid("wk_scan: hop < 1");
+  if (n_rec < 0) return invalid("wk_scan: n_rec < 0");
+  if (n_samples < 0 || n_samples > kScanMaxSamples) return invalid("wk_scan: n_samples outside [0, 2^30]");
+  return WK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+wk_status wk_scan_workspace_bytes(int64_t n_rec, int64_t n_samples, int32_t hop, int64_t windows_per_chunk,
+                                  size_t* bytes) {
+  if (!bytes) return invalid("wk_scan_workspace_bytes: null bytes");
+  *bytes = 0;
+  wk_status s = scan_check_geometry(n_rec, n_samples, hop);
+  if (s != WK_OK) return s;
+  if (windows_per_chunk < 0) return invalid("wk_scan_workspace_bytes: windows_per_chunk < 0");
+  const ScanPlan p = scan_plan(n_rec, n_samples, hop);
+  if (!p.shared) return WK_OK;   // forwarded to the wk_forward path: no workspace
+  const int64_t total = n_rec * p.W;
+  int64_t wpc = windows_per_chunk ? windows_per_chunk : kScanChunkWindows;
+  if (wpc > total) wpc = total;
+  *bytes = p.store_bytes + (size_t)wpc * kScanFeatBytes;
+  return WK_OK;
+}
+
+wk_status wk_scan(wk_handle* h, const void* d_audio, int32_t dtype, int64_t n_rec, int64_t n_samples,
+                  int64_t rec_stride, int32_t hop, float* d_logits, float* d_feats_or_null, void* d_workspace,
+                  size_t workspace_bytes, void* stream) {
+  if (!h) return invalid("wk_scan: null handle");
+  if (h->cfg.mode != WK_MODE_TORCHAUDIO_CMVN) {
+    g_last_error = "wk_scan: the xiaoa CNN consumes mode-B (torchaudio+CMVN) features";
+    return WK_ERR_UNSUPPORTED;
+  }
+  if (!h->d_weights) return invalid("wk_scan: handle created without weights");
+  wk_status s = scan_check_geometry(n_rec, n_samples, hop);
+  if (s != WK_OK) return s;
+  if (dtype != WK_DTYPE_F32 && dtype != WK_DTYPE_I16) return invalid("wk_scan: bad dtype");
+  if (n_rec > 1 && rec_stride < n_samples) return invalid("wk_scan: rec_stride < n_samples");
+  const ScanPlan p = scan_plan(n_rec, n_samples, hop);
+  if (p.W == 0 || n_rec == 0) return WK_OK;
+  if (!d_audio || !d_logits) return invalid("wk_scan: null audio / logits");
+  const bool i16 = dtype == WK_DTYPE_I16;
+  const size_t esz = i16 ? 2 : 4;
+  if (!p.shared) {
+    // No frame of one window is a frame of another: the sliding wk_forward, per recording.
+    for (int64_t r = 0; r < n_rec; ++r) {
+      s = forward_impl(h, (const char*)d_audio + (size_t)(r * rec_stride) * esz, dtype, p.W, WK_WIN_SAMPLES, hop,
+                       d_logits + r * p.W, d_feats_or_null ? d_feats_or_null + r * p.W * 13 * 63 : nullptr, stream,
+                       h->err.dev());
+      if (s != WK_OK) return s;
+    }
+    return WK_OK;
+  }
+  const int64_t total = n_rec * p.W;
+  if (!d_workspace || workspace_bytes < p.store_bytes + kScanFeatBytes)
+    return invalid("wk_scan: workspace smaller than wk_scan_workspace_bytes(..., 1 window per chunk)");
+  int64_t wpc = (int64_t)((workspace_bytes - p.store_bytes) / kScanFeatBytes);
+  if (wpc > total) wpc = total;
+  // Chunks are whole work units of wpu consecutive windows of one recording
+  // (the last unit of a recording may hold fewer), contiguous in the flat
+  // [n_rec][W] order, so each chunk is one CNN launch.
+  const int wpu = (int)(wpc < kScanUnitWindows ? wpc : kScanUnitWindows);
+  const int64_t units_per_rec = (p.W + wpu - 1) / wpu;
+  const int64_t n_units = n_rec * units_per_rec;
+  const int64_t units_per_chunk = wpc / wpu;
+  auto flat_of = [&](int64_t u) { return (u / units_per_rec) * p.W + (u % units_per_rec) * wpu; };
+  float* store = (float*)d_workspace;
+  float* chunk_feats = (float*)((char*)d_workspace + p.store_bytes);
+  const hipStream_t st = (hipStream_t)stream;
+  return on_device(h->cfg.device, [&]() -> wk_status {
+    hipError_t e = launch_scan_frames(i16, d_audio, n_rec, rec_stride, p.G, p.g_pad, store, 2 * h->n_cu, st);
+    if (e != hipSuccess) return hip_fail(e, "scan frames launch");
+    for (int64_t u0 = 0; u0 < n_units; u0 += units_per_chunk) {
+      const int64_t u1 = u0 + units_per_chunk < n_units ? u0 + units_per_chunk : n_units;
+      const int64_t flat0 = flat_of(u0), n = (u1 == n_units ? total : flat_of(u1)) - flat0;
+      float* feats = d_feats_or_null ? d_feats_or_null + flat0 * 13 * 63 : chunk_feats;
+      e = launch_scan_assemble(i16, d_audio, rec_stride, hop, p.W, wpu, u0, u1 - u0, flat0, p.g_pad, store, feats,
+                               2 * h->n_cu, st);
+      if (e != hipSuccess) return hip_fail(e, "scan assemble launch");
+      if ((e = launch_cnn(h, feats, n, d_logits + flat0, st, h->err.dev())) != hipSuccess)
+        return hip_fail(e, "cnn launch");
+    }
+    return WK_OK;
+  });
+}
+
+}  // extern "C"

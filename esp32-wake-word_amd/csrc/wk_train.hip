@@ -32,7 +32,10 @@
 
 #include <math.h>
 
+#include <memory>
 #include <new>
+
+#include "wk_devmem.h"
 
 namespace wk {
 namespace {
@@ -334,12 +337,12 @@ hipError_t launch_pack_direct(const float* w, float* pk, int count, hipStream_t 
 struct wk_trainer {
   int device = 0;
   int grid_cap = 512;        // workgroups per gradient launch
-  float* d_w = nullptr;      // [WK_NUM_WEIGHTS] current weights
-  float* d_pk = nullptr;     // fragment-major copy (launch_pack_direct)
-  float* d_g = nullptr;      // last gradients
-  float* d_m = nullptr;      // AdamW first / second moments
-  float* d_v = nullptr;
-  float* d_part = nullptr;   // [part_slots][kSlot] workgroup partial sums
+  wk::DevBuf<float> d_w;      // [WK_NUM_WEIGHTS] current weights
+  wk::DevBuf<float> d_pk;     // fragment-major copy (launch_pack_direct)
+  wk::DevBuf<float> d_g;      // last gradients
+  wk::DevBuf<float> d_m;      // AdamW first / second moments
+  wk::DevBuf<float> d_v;
+  wk::DevBuf<float> d_part;   // [part_slots][kSlot] workgroup partial sums
   int64_t part_slots = 0;
   int64_t steps = 0;
   bool have_grads = false;
@@ -348,11 +351,6 @@ struct wk_trainer {
 using wk::hip_fail;
 using wk::invalid;
 
-static void trainer_free(wk_trainer* t) {
-  for (float* p : {t->d_w, t->d_pk, t->d_g, t->d_m, t->d_v, t->d_part})
-    if (p) (void)hipFree(p);
-}
-
 extern "C" {
 
 wk_status wk_trainer_create(int32_t device, const float* host_weights, wk_trainer** out) {
@@ -360,45 +358,36 @@ wk_status wk_trainer_create(int32_t device, const float* host_weights, wk_traine
   *out = nullptr;
   if (!host_weights) return invalid("wk_trainer_create: null weights");
   if (device < 0) return invalid("wk_trainer_create: bad device");
-  wk_trainer* t = new (std::nothrow) wk_trainer;
-  if (!t) return WK_ERR_NO_MEMORY;
-  t->device = device;
-  const wk_status s = wk::on_device(device, [&]() -> wk_status {
+  return wk::on_device(device, [&]() -> wk_status {
+    std::unique_ptr<wk_trainer> t(new (std::nothrow) wk_trainer);   // (a failed create frees it here, device current)
+    if (!t) return WK_ERR_NO_MEMORY;
+    t->device = device;
     hipError_t e;
     const size_t nb = sizeof(float) * wk::kNumWeights;
     int cu = 256;
     if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cu > 0)
       t->grid_cap = 2 * cu;
-    if ((e = hipMalloc(&t->d_w, nb)) != hipSuccess || (e = hipMalloc(&t->d_g, nb)) != hipSuccess ||
-        (e = hipMalloc(&t->d_m, nb)) != hipSuccess || (e = hipMalloc(&t->d_v, nb)) != hipSuccess ||
-        (e = hipMalloc(&t->d_pk, sizeof(float) * wk::kTrainPacked)) != hipSuccess)
+    if ((e = t->d_w.alloc(wk::kNumWeights)) != hipSuccess || (e = t->d_g.alloc(wk::kNumWeights)) != hipSuccess ||
+        (e = t->d_m.alloc(wk::kNumWeights)) != hipSuccess || (e = t->d_v.alloc(wk::kNumWeights)) != hipSuccess ||
+        (e = t->d_pk.alloc(wk::kTrainPacked)) != hipSuccess)
       return e == hipErrorOutOfMemory ? wk::fail(WK_ERR_NO_MEMORY, "wk_trainer_create: hipMalloc") : hip_fail(e, "wk_trainer_create: hipMalloc");
     if ((e = hipMemcpy(t->d_w, host_weights, nb, hipMemcpyHostToDevice)) != hipSuccess ||
         (e = hipMemset(t->d_m, 0, nb)) != hipSuccess || (e = hipMemset(t->d_v, 0, nb)) != hipSuccess ||
         (e = hipDeviceSynchronize()) != hipSuccess)
       return hip_fail(e, "wk_trainer_create: upload");
+    *out = t.release();
     return WK_OK;
   });
-  if (s != WK_OK) {
-    (void)wk::on_device(device, [&]() -> wk_status {
-      trainer_free(t);
-      return WK_OK;
-    });
-    delete t;
-    return s;
-  }
-  *out = t;
-  return WK_OK;
 }
 
 wk_status wk_trainer_destroy(wk_trainer* t) {
   if (!t) return invalid("wk_trainer_destroy: null trainer");
-  (void)wk::on_device(t->device, [&]() -> wk_status {
+  const wk_status s = wk::on_device(t->device, [&]() -> wk_status {
     (void)hipDeviceSynchronize();
-    trainer_free(t);
+    delete t;
     return WK_OK;
   });
-  delete t;
+  if (s != WK_OK) delete t;   // the device could not be made current: the object goes all the same
   return WK_OK;
 }
 
@@ -413,10 +402,8 @@ wk_status wk_trainer_grad(wk_trainer* t, const float* d_feats, const float* d_la
     const int grid = (int)(batch < t->grid_cap ? batch : t->grid_cap);
     if (grid > t->part_slots) {   // workspace grows on the first call with a larger batch (then reused)
       if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(e, "wk_trainer_grad: sync");
-      if (t->d_part) (void)hipFree(t->d_part);
-      t->d_part = nullptr;
       t->part_slots = 0;
-      if ((e = hipMalloc(&t->d_part, sizeof(float) * (size_t)grid * wk::kSlot)) != hipSuccess)
+      if ((e = t->d_part.alloc((size_t)grid * wk::kSlot)) != hipSuccess)
         return e == hipErrorOutOfMemory ? wk::fail(WK_ERR_NO_MEMORY, "wk_trainer_grad: workspace") : hip_fail(e, "wk_trainer_grad: workspace");
       t->part_slots = grid;
     }
