@@ -3,6 +3,7 @@
 // See wk_frontend.hip for the algorithm and the reference citations.
 #pragma once
 #include "wk_common.h"
+#include "wk_fe_lds_layout.h"
 #include "wk_tables.h"
 
 namespace wk {
@@ -131,19 +132,36 @@ __device__ __forceinline__ float row_rol1(float v) {  // lane l <- lane (l+1) mo
   return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x12F, 0xF, 0xF, false));
 }
 
-// LDS tables shared by the workgroup (fe_init_tables).
+// Tables of the workgroup (fe_init_tables; layout: wk_fe_lds_layout.h), as
+// this lane sees them.
 struct FeTables {
-  const float* win;   // [320] analysis window, odd rows n1 negated in lanes j >= 8 (kWinB / kWinA)
-  const float* tw;    // [16 slots][16 lanes][2]: W256^(j * (s ^ (j & 8)))
+  // Analysis window, odd rows n1 negated in lanes j >= 8 (kWinB / kWinA).
+  // fe_stage0: the constant table [320] (the standalone kernels read it from
+  // L1).  fe_stage0_fused: this lane's window row in LDS, fe_lds::win_row_off(j).
+  const float* win;
+  // This lane's twiddle row in LDS, fe_lds::row_off(j): W256^(j * (s ^ (j & 8))),
+  // s = 0..15, then fe_split_tw(j, k2), k2 = 0..7.
+  const float* row;
 };
 
-// Split twiddles tws(k2, j) = fe_split_tw(j, k2), k2 = 1..7: the [7][16] f2 table in LDS.
-struct TwsLds {
-  const float* p;
-  __device__ __forceinline__ f2 operator()(int k2, int j) const {
-    return *reinterpret_cast<const f2*>(p + ((k2 - 1) * 16 + j) * 2);
-  }
-};
+// Two adjacent {re, im} table entries as one 16-byte LDS read (ds_read_b128):
+// p is 16-byte aligned (fe_lds: row pitches and entry offsets are multiples of
+// 4 floats), and the 16 lanes j of each of the read's lane groups fall on 16
+// distinct bank quads.
+// Written as two 8-byte loads from an address assumed 16-byte aligned, which
+// the load vectoriser joins into the one ds_read_b128 (checked in the ISA:
+// no table read may be a ds_read2_b64).  Written as one float4 load, the
+// entries reach the arithmetic as shuffles of the loaded vector, and the fp32
+// unit's compiler then no longer contracted the window product of row 9 into
+// the first DFT16 butterflies (a[1] +- y9 w9 as two v_pk_fma_f32): different
+// roundings, different bits.  With this form every unit compiles to the same
+// floating-point operations as with the slot-major tables
+// (tests/test_gpu_fe_bits.py holds it to them).
+__device__ __forceinline__ void lds_pair16(const float* p, f2& a, f2& b) {
+  const f2* q = reinterpret_cast<const f2*>(__builtin_assume_aligned(p, 16));
+  a = q[0];
+  b = q[1];
+}
 
 // The real-FFT split pairs bin k = j + 16 k2 (lane j, register k2) with bin
 // 256 - k (lane (16 - j) & 15).  After the one-pass transpose of fe_rest the
@@ -158,13 +176,6 @@ __device__ __forceinline__ f2 fe_split_tw(int j, int k2) {   // W512^(j + 16 k2)
   float sn, cs;
   sincospif(-(float)(j + 16 * k2) / 256.0f, &sn, &cs);
   return fe_split_flip(j, k2) ? f2{-cs, sn} : f2{cs, sn};
-}
-__device__ __forceinline__ void fe_init_tws(float* tws, int tid, int nthreads) {
-  for (int i = tid; i < 7 * 16; i += nthreads) {
-    const f2 w = fe_split_tw(i % 16, i / 16 + 1);
-    tws[2 * i] = w.x;
-    tws[2 * i + 1] = w.y;
-  }
 }
 
 // Stage 0: pre-emphasis + window of the 320 frame samples as 160 complex
@@ -298,10 +309,11 @@ __device__ __forceinline__ void fe_stage0_rows(const Raw<T>& raw, int lane, cons
 template <typename T>
 __device__ __forceinline__ void fe_stage0_fused(const Raw<T>& raw, int lane, int edge, const FeTables& tb,
                                                 f2 (&a)[16], float pre = -0.97f) {
-  // All ten window pairs are read up front (see fe_stage0).
+  // All ten window pairs are read up front (see fe_stage0): this lane's
+  // window row, five 16-byte reads.
   f2 w[10];
 #pragma unroll
-  for (int n1 = 0; n1 < 10; ++n1) w[n1] = *reinterpret_cast<const f2*>(tb.win + 32 * n1 + 2 * (lane & 15));
+  for (int n1 = 0; n1 < 10; n1 += 2) lds_pair16(tb.win + fe_lds::win_off(0, n1), w[n1], w[n1 + 1]);
   // The windowed pairs are formed in each branch, so the paths merge on a[]
   // (register pairs), as in fe_stage0.
   if (edge == 0) fe_stage0_rows<0>(raw, lane, w, a, pre);
@@ -315,7 +327,7 @@ __device__ __forceinline__ void fe_stage0_fused(const Raw<T>& raw, int lane, int
 // complex arithmetic is packed fp32 (see f2 in wk_common.h).
 // xs: 8-byte aligned transpose scratch of 270 floats inside the frame's row
 // (row + 0 or row + 1; kPRow = 271).
-// w0: fe_split_tw(j, 0); tws(k2, j): fe_split_tw(j, k2), k2 = 1..7.
+// tb.row: this lane's twiddle row (W256 twiddles, then fe_split_tw(j, k2), k2 = 0..7).
 // pf(k), k = 0..3, is called at four points of the round (prefetch parts);
 // pf(-1) just before the round's first write into the row.
 //
@@ -331,14 +343,34 @@ __device__ __forceinline__ void fe_stage0_fused(const Raw<T>& raw, int lane, int
 // of the other at 17 (n2 & 7) + (k1 ^ 8): lane-uniform immediate offsets for
 // the writes (base 17 (j & 7) + h, offset s) and the reads (base kc or kc ^ 8,
 // offset 17 s), each 16 lanes on 16 distinct 8-byte bank pairs, and 135
-// f2 = 270 floats, inside the frame's own row.  Per round: 8 ds_write2_b64 +
-// 8 ds_read2_b64 (the re / im two-pass transpose was 16 write2 + 32 reads).
+// f2 = 270 floats, inside the frame's own row (the re / im two-pass transpose
+// was 16 write2 + 32 reads).
 // The second DFT16 then sees its inputs rotated by 8 in lanes kc >= 8, which
 // multiplies Z[kc + 16 k2] by (-1)^k2 there; fe_split_tw absorbs the sign.
-template <bool MODE_B, typename PF, typename TWS>
+//
+// LDS traffic of one wave-round, in instructions and LDS-array cycles
+// (MI355X: ds_read_b128 4, ds_read_b64 2, ds_read2_b64 8 per wave-instruction):
+//   window (fused kernel)   5 ds_read_b128    20     (was 5 ds_read2_b64, 40)
+//   W256 twiddles           8 ds_read_b128    32     (was 8 ds_read2_b64, 64)
+//   split twiddles          4 ds_read_b128    16     (was 3 ds_read2_b64 + 1 ds_read_b64, 26; w0 in 2 VGPRs)
+//   transpose writes        8 ds_write2_b64
+//   transpose reads         8 ds_read2_b64    64
+//   power-row stores        ds_write2_b32 / ds_write_b32
+// The tables are lane-major (wk_fe_lds_layout.h) so that a lane's entries are
+// one row read 16 bytes at a time at immediate offsets from tb.row / tb.win:
+// SQ_LDS_IDX_ACTIVE per window 7,559 -> 6,618 (16 wave-rounds x 62 cycles
+// predicted 992), bank conflicts unchanged; fp32 +2.0 %, bf16 +1.3 %,
+// bit-identical (profiles/lds_tables_ab.md).
+// The transposes' reads stay the pairs the compiler forms.  As 16 single
+// ds_read_b64 (volatile LDS loads, which it does not pair) they are served
+// per 32-lane half, and a half holds two frame groups whose rows, 16 x 271
+// floats apart, start 48 banks apart: 8 of each group's 16 bank pairs are the
+// other's (2-way, and the row pitch cannot change).  Measured so:
+// SQ_LDS_BANK_CONFLICT per window 440 -> 936, array cycles up, fp32 +0.1 %
+// over the tables alone (noise), bf16 -2.4 %; not kept.
+template <bool MODE_B, typename PF>
 __device__ __forceinline__ void fe_rest(f2 (&a)[16], int j, float* __restrict__ row, float* __restrict__ xs,
-                                        const FeTables& tb, f2 w0, const TWS& tws, int esp_pack,
-                                        const PF& pf WK_SP_PARAM) {
+                                        const FeTables& tb, int esp_pack, const PF& pf WK_SP_PARAM) {
   pf(0);
   dft16(a);  // slot s: A[s ^ (j & 8)] at a[dft16_out(s)]
   WK_FE_HIT(2);
@@ -346,12 +378,18 @@ __device__ __forceinline__ void fe_rest(f2 (&a)[16], int j, float* __restrict__ 
   // twiddle W256^(n2 k1), n2 = j, k1 = s ^ (j & 8); each half is twiddled
   // just before it is written (fewer live registers)
   f2* x2 = reinterpret_cast<f2*>(xs);
-  const int wb = 17 * (j & 7) + (j & 8);
-  auto tw = [&](int s) { return cmul2(a[dft16_out(s)], *reinterpret_cast<const f2*>(tb.tw + (s * 16 + j) * 2)); };
+  const int wb = fe_lds::xpose_wr(j);
+  // slots s0, s0 + 1: one 16-byte read of the lane's twiddle row feeds both products
+  auto tw2 = [&](int s0, f2& b0, f2& b1) {
+    f2 wa, wc;
+    lds_pair16(tb.row + fe_lds::tw_off(0, s0), wa, wc);
+    b0 = cmul2(a[dft16_out(s0)], wa);
+    b1 = cmul2(a[dft16_out(s0 + 1)], wc);
+  };
   f2 b[8];
   if constexpr (!WK_FE_STAGED) pf(1);
 #pragma unroll
-  for (int s = 0; s < 8; ++s) b[s] = tw(s);
+  for (int s = 0; s < 8; s += 2) tw2(s, b[s], b[s + 1]);
   pf(-1);   // the first write into this frame's LDS row follows (fused kernel: wait until the row is free)
 #pragma unroll
   for (int s = 0; s < 8; ++s) x2[wb + s] = b[s];
@@ -360,7 +398,7 @@ __device__ __forceinline__ void fe_rest(f2 (&a)[16], int j, float* __restrict__ 
   f2 c[16];
   wave_lds_sync();
 #pragma unroll
-  for (int s = 0; s < 8; ++s) c[s] = x2[j + 17 * s];
+  for (int s = 0; s < 8; ++s) c[s] = x2[fe_lds::xpose_rd(j, s)];
   // The packed unit issues prefetch parts 1-3 one step earlier than the
   // scalar unit (part 1 before the twiddles, part 2 after these reads, part 3
   // before the second DFT16 rather than after it): the loads get ~1 k more
@@ -369,13 +407,13 @@ __device__ __forceinline__ void fe_rest(f2 (&a)[16], int j, float* __restrict__ 
   // measured -0.5 to 0 % with the earlier parts 2-3.
   if constexpr (!WK_FE_STAGED) pf(2);
 #pragma unroll
-  for (int s = 8; s < 16; ++s) b[s - 8] = tw(s);
+  for (int s = 8; s < 16; s += 2) tw2(s, b[s - 8], b[s - 7]);
   wave_lds_sync();
 #pragma unroll
   for (int s = 8; s < 16; ++s) x2[wb + s - 8] = b[s - 8];
   wave_lds_sync();
 #pragma unroll
-  for (int s = 8; s < 16; ++s) c[s] = x2[(j ^ 8) + 17 * (s - 8)];
+  for (int s = 8; s < 16; ++s) c[s] = x2[fe_lds::xpose_rd(j ^ 8, s - 8)];
   wave_lds_sync();
   WK_FE_HIT(4);
 
@@ -397,7 +435,9 @@ __device__ __forceinline__ void fe_rest(f2 (&a)[16], int j, float* __restrict__ 
   // Partner: lane (16-j)&15 of this group, register 15-k2, fetched by two DPP
   // row moves (row_mirror: j <- 15-j, then row_shr:1: j <- j-1), no LDS trip;
   // lane 0 holds its own partner in register (16-k2)&15.  The twiddle is one
-  // value per (lane, k2) (w0 / tws), sign-adjusted by fe_split_tw.
+  // value per (lane, k2), sign-adjusted by fe_split_tw: the second part of
+  // the lane's twiddle row, read two entries at a time (wsp) by the first
+  // group of chains that needs them.
   f2 sc0 = {1.0f, 1.0f}, sc = {1.0f, 1.0f};
   if constexpr (!MODE_B) {
     // mfcc.c:267 power = |X|^2 / n_fft + 1e-12 = |U|^2 / 2048 + 1e-12; the
@@ -424,9 +464,13 @@ __device__ __forceinline__ void fe_rest(f2 (&a)[16], int j, float* __restrict__ 
   // r06m_staged_ab.txt); the packed fp32 unit measured -0.1 % with it, so
   // it keeps the per-chain order.
   constexpr int G = 3;
+  f2 wsp[8];
 #pragma unroll
   for (int k0 = 0; k0 < 8; k0 += G) {
     f2 S[G], D[G], pw[G];
+#pragma unroll
+    for (int q = 0; q < 8; q += 2)
+      if (q / G * G == k0) lds_pair16(tb.row + fe_lds::split_off(0, q), wsp[q], wsp[q + 1]);
 #if WK_FE_STAGED
     // the partners' row_mirror moves of the group first, then their row_shr
     // moves (a DPP read of a VGPR written by the previous VALU op waits 2 states)
@@ -476,7 +520,7 @@ __device__ __forceinline__ void fe_rest(f2 (&a)[16], int j, float* __restrict__ 
 #pragma unroll
     for (int t = 0; t < G; ++t)
       if (k0 + t <= 7) {
-        wt[t] = k0 + t == 0 ? w0 : tws(k0 + t, j);
+        wt[t] = wsp[k0 + t];
         tt[t] = cmul2_a(D[t], wt[t]);
       }
 #pragma unroll
@@ -503,7 +547,7 @@ __device__ __forceinline__ void fe_rest(f2 (&a)[16], int j, float* __restrict__ 
     for (int t = 0; t < G; ++t) {
       const int k2 = k0 + t;
       if (k2 > 7) continue;
-      const f2 bb = cmul2(D[t], k2 == 0 ? w0 : tws(k2, j));
+      const f2 bb = cmul2(D[t], wsp[k2]);
       const f2 uvx = fma2(by(bb), f2{1.0f, -1.0f}, bx(S[t]));
       const f2 uvy = fma2(bx(bb), f2{-1.0f, 1.0f}, by(S[t]));
       pw[t] = fma2(uvx, uvx, uvy * uvy);
@@ -565,35 +609,52 @@ __device__ __forceinline__ void cmvn_lane2(float& v0, float& v1, bool valid, int
   v1 = d1 * (1.0f / (s1 + 1e-8f));
 }
 
-// LDS carve (floats): twiddles | split twiddles | log-mel [40][64] | power
-// rows [63][271] | window.  The standalone front-end stops before the window
-// (it reads the window from the constant table: kFeLdsNoWin keeps two
-// workgroups per CU); the fused kernel copies it to LDS.
-constexpr int kTwOff = 0, kTwSize = 16 * 16 * 2;
-constexpr int kTwsOff = kTwOff + kTwSize, kTwsSize = 7 * 16 * 2;
-constexpr int kLOff = kTwsOff + kTwsSize, kLSize = 40 * WK_LSTRIDE;
-constexpr int kPOff = kLOff + kLSize, kPSize = kNFramesB * kPRow;
-constexpr int kFeLdsNoWin = kPOff + kPSize;
-constexpr int kWinOff = (kFeLdsNoWin + 1) & ~1, kWinSize = 320;
-constexpr int kFeLds = kWinOff + kWinSize;
-static_assert(kFeLdsNoWin * 4 <= 81920, "standalone front-end LDS must allow 2 workgroups per CU");
+// LDS carve (floats; fe_lds::carve): twiddle rows [16 lanes][52] | log-mel
+// [40][64] | power rows [63][271] | window rows [16 lanes][20].  The standalone
+// front-end stops before the window (it reads the window from the constant
+// table: kFeLdsNoWin keeps two workgroups per CU); the fused kernel copies it
+// to LDS.
+constexpr fe_lds::Carve kFeCarve = fe_lds::carve(WK_LSTRIDE, kNFramesB, kPRow);
+constexpr int kTabOff = kFeCarve.tab, kTabSize = fe_lds::kTabSize;
+constexpr int kLOff = kFeCarve.logmel, kLSize = 40 * WK_LSTRIDE;
+constexpr int kPOff = kFeCarve.power, kPSize = kNFramesB * kPRow;
+constexpr int kFeLdsNoWin = kFeCarve.end_no_win;
+constexpr int kWinOff = kFeCarve.win, kWinSize = fe_lds::kWinSize;
+constexpr int kFeLds = kFeCarve.end;
+static_assert(kFeLdsNoWin * 4 <= fe_lds::kStandaloneLimitBytes, "standalone front-end LDS must allow 2 workgroups per CU");
 static_assert(kLOff % 4 == 0, "log-mel rows are read with ds_read_b128");
-static_assert(kPOff % 2 == 0 && kPRow % 2 == 1 && kPRow >= 271,
+static_assert(kTabOff % 4 == 0 && fe_lds::kRowPitch % 4 == 0 && kWinOff % 4 == 0 && fe_lds::kWinPitch % 4 == 0,
+              "table rows are read with ds_read_b128 (the carve's base is 16-byte aligned)");
+static_assert(kPOff % 2 == 0 && kPRow % 2 == 1 && kPRow >= fe_lds::kXposeFloats + 1,
               "row f's transpose scratch is row + (f & 1): 8-byte aligned, 270 floats");
 
-// Fill the twiddle tables (and the window, WIN) of the LDS carve (all threads of the WG).
+// Fill the twiddle rows (and the window rows, WIN) of the LDS carve (all threads of the WG).
 template <bool MODE_B, bool WIN>
 __device__ __forceinline__ void fe_init_tables(float* smem, int tid, int nthreads) {
   if (WIN)
-    for (int i = tid; i < 320; i += nthreads) smem[kWinOff + i] = MODE_B ? kWinB[i] : kWinA[i];
+    for (int i = tid; i < 320; i += nthreads) {
+      const int n1 = i / 32, jj = (i % 32) / 2, c = i & 1;   // i == fe_lds::win_src(jj, n1) + c
+      smem[kWinOff + fe_lds::win_off(jj, n1) + c] = MODE_B ? kWinB[i] : kWinA[i];
+    }
   for (int i = tid; i < 16 * 16; i += nthreads) {
     const int s = i / 16, jj = i % 16, k1 = s ^ (jj & 8);
     float sn, cs;
     sincospif(-(float)(jj * k1) / 128.0f, &sn, &cs);
-    smem[kTwOff + 2 * i] = cs;
-    smem[kTwOff + 2 * i + 1] = sn;
+    smem[kTabOff + fe_lds::tw_off(jj, s)] = cs;
+    smem[kTabOff + fe_lds::tw_off(jj, s) + 1] = sn;
   }
-  fe_init_tws(smem + kTwsOff, tid, nthreads);
+  for (int i = tid; i < 8 * 16; i += nthreads) {
+    const int k2 = i / 16, jj = i % 16;
+    const f2 w = fe_split_tw(jj, k2);
+    smem[kTabOff + fe_lds::split_off(jj, k2)] = w.x;
+    smem[kTabOff + fe_lds::split_off(jj, k2) + 1] = w.y;
+  }
+}
+
+// The tables as lane j sees them.  win: the constant table (standalone
+// kernels, fe_stage0) or null = the window rows in LDS (fused kernel, fe_stage0_fused).
+__device__ __forceinline__ FeTables fe_tables(const float* smem, int j, const float* win_const) {
+  return {win_const ? win_const : smem + kWinOff + fe_lds::win_row_off(j), smem + kTabOff + fe_lds::row_off(j)};
 }
 
 }  // namespace wk

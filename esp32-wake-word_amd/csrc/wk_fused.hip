@@ -255,9 +255,7 @@ __device__ __forceinline__ void fe_role(float* smem, const T* __restrict__ audio
   float* L1 = smem + kL1Off;
   unsigned* ctrl = reinterpret_cast<unsigned*>(smem + kCtrlOff);
   const int g = lane >> 4, j = lane & 15;
-  const FeTables tb = {smem + kWinOff, smem + kTwOff};
-  const TwsLds tws = {smem + kTwsOff};
-  const f2 w0 = fe_split_tw(j, 0);
+  const FeTables tb = fe_tables(smem, j, nullptr);   // window and twiddle rows of lane j, both in LDS
   const int slot_base = 16 * (g & 1) + 32 * (g >> 1);
   // frame slot of this wave (moving the edge frames to other waves measured neutral), its rounds r0..r1
   const int fw = FEW == 8 || wave < 8 ? wave : wave - 4;
@@ -348,7 +346,7 @@ __device__ __forceinline__ void fe_role(float* smem, const T* __restrict__ audio
       };
       WK_STAMP(1);
       float* row = fl < kNFramesB ? P + fl * kPRow : smem + kDummyRowOff;
-      fe_rest<true>(a, j, row, row + (fl & 1), tb, w0, tws, 0, pf_part WK_SP_ARG);
+      fe_rest<true>(a, j, row, row + (fl & 1), tb, 0, pf_part WK_SP_ARG);
     }
     role_sync<kPrioFe, FEW>(ctrl, kCtrlFeBar, gen, lane);               // all power rows of clip i written
     WK_STAMP(7);

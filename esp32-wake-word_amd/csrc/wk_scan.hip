@@ -49,9 +49,7 @@ __global__ __launch_bounds__(kFeBlock, 4) void wk_scan_frames_kernel(const T* __
   const int g = lane >> 4, j = lane & 15;
 
   fe_init_tables<true, false>(smem, threadIdx.x, kFeBlock);
-  const FeTables tb = {kWinB, smem + kTwOff};
-  const TwsLds tws = {smem + kTwsOff};
-  const f2 w0 = fe_split_tw(j, 0);
+  const FeTables tb = fe_tables(smem, j, kWinB);
   __syncthreads();
 
   // Unit u = (recording, chunk): global frames g0 .. g0 + nfc - 1, g0 = 1 + 63*chunk.
@@ -94,7 +92,7 @@ __global__ __launch_bounds__(kFeBlock, 4) void wk_scan_frames_kernel(const T* __
       if (fl < nfc) fe_stage0<true>(pf, 256 * fl + 2, 0, j, false, tb, a);
       // pf is consumed: prefetch the next wave-round, (u,1) or (u+grid,0), into it.
       prefetch(r == 0 ? u : u + gridDim.x, r ^ 1, pf);
-      if (fl < nfc) fe_rest<true>(a, j, P + fl * kPRow, P + fl * kPRow + (fl & 1), tb, w0, tws, 0, NoPrefetch());
+      if (fl < nfc) fe_rest<true>(a, j, P + fl * kPRow, P + fl * kPRow + (fl & 1), tb, 0, NoPrefetch());
     }
     wg_barrier_lds();
 
@@ -134,9 +132,7 @@ __global__ __launch_bounds__(kFeBlock, 4) void wk_scan_assemble_kernel(const T* 
   const int g = lane >> 4, j = lane & 15;
 
   fe_init_tables<true, false>(smem, threadIdx.x, kFeBlock);
-  const FeTables tb = {kWinB, smem + kTwOff};
-  const TwsLds tws = {smem + kTwsOff};
-  const f2 w0 = fe_split_tw(j, 0);
+  const FeTables tb = fe_tables(smem, j, kWinB);
   __syncthreads();
 
   for (int64_t uu = blockIdx.x; uu < n_units; uu += gridDim.x) {
@@ -160,7 +156,7 @@ __global__ __launch_bounds__(kFeBlock, 4) void wk_scan_assemble_kernel(const T* 
         load_raw<true>(rs, base, j, kWinSamples, true, true, raw, (e >> 1) * hop);
         f2 a[16];
         fe_stage0<true>(raw, base, kWinSamples, j, true, tb, a);
-        fe_rest<true>(a, j, P + e * kPRow, P + e * kPRow + (e & 1), tb, w0, tws, 0, NoPrefetch());
+        fe_rest<true>(a, j, P + e * kPRow, P + e * kPRow + (e & 1), tb, 0, NoPrefetch());
       }
     }
     wg_barrier_lds();
