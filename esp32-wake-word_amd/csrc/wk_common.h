@@ -7,8 +7,10 @@ namespace wk {
 
 constexpr int kWinSamples = 16000;   // 1 s @ 16 kHz (extract_mfcc.py:157)
 constexpr int kNFramesB = 63;        // 1 + 16000/256 with center=True
-constexpr int kPRow = 271;           // LDS pitch of one frame's power row (odd: lane-per-frame reads
-                                     // conflict-free; >=271 so the 16x17 transpose scratch fits)
+constexpr int kPRow = 270;           // LDS pitch of one frame's power row = the 16x17 transpose scratch
+                                     // (fe_lds::kXposeFloats).  Even, so every row is 8-byte aligned and the
+                                     // mel reads it as pairs of bins (ds_read_b64); 270 = 14 mod 64 keeps the
+                                     // 32 lane-per-frame reads of a half on 32 distinct bank pairs
 constexpr int kFeBlock = 512;        // 8 waves per front-end workgroup
 
 // Complex values live in VGPR pairs as float2 {re, im}: the front-end's

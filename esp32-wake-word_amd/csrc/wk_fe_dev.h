@@ -325,8 +325,7 @@ __device__ __forceinline__ void fe_stage0_fused(const Raw<T>& raw, int lane, int
 
 // Stages 1..4 of one frame -> its power row (bins 0..256) in LDS.  All
 // complex arithmetic is packed fp32 (see f2 in wk_common.h).
-// xs: 8-byte aligned transpose scratch of 270 floats inside the frame's row
-// (row + 0 or row + 1; kPRow = 271).
+// The row (8-byte aligned, kPRow = 270 floats) is also the transpose scratch.
 // tb.row: this lane's twiddle row (W256 twiddles, then fe_split_tw(j, k2), k2 = 0..7).
 // pf(k), k = 0..3, is called at four points of the round (prefetch parts);
 // pf(-1) just before the round's first write into the row.
@@ -355,7 +354,13 @@ __device__ __forceinline__ void fe_stage0_fused(const Raw<T>& raw, int lane, int
 //   split twiddles          4 ds_read_b128    16     (was 3 ds_read2_b64 + 1 ds_read_b64, 26; w0 in 2 VGPRs)
 //   transpose writes        8 ds_write2_b64
 //   transpose reads         8 ds_read2_b64    64
-//   power-row stores        ds_write2_b32 / ds_write_b32
+//   power-row stores        ds_write2_b32 / ds_write_b32 (the two frame groups of a half on
+//                           disjoint banks: fe_lds::frame_slot)
+// and per clip, in the mel (lane = frame, wk_tables.h): 159 ds_read_b64 of
+// aligned bin pairs over the 8 waves, 318 cycles (were 153 ds_read2_b32 + 6
+// ds_read_b32, 624: the row pitch was odd, 271, so every second row was only
+// 4-byte aligned).  The pitch is 270 = the transpose scratch, which is now the
+// row itself.
 // The tables are lane-major (wk_fe_lds_layout.h) so that a lane's entries are
 // one row read 16 bytes at a time at immediate offsets from tb.row / tb.win:
 // SQ_LDS_IDX_ACTIVE per window 7,559 -> 6,618 (16 wave-rounds x 62 cycles
@@ -363,21 +368,22 @@ __device__ __forceinline__ void fe_stage0_fused(const Raw<T>& raw, int lane, int
 // bit-identical (profiles/lds_tables_ab.md).
 // The transposes' reads stay the pairs the compiler forms.  As 16 single
 // ds_read_b64 (volatile LDS loads, which it does not pair) they are served
-// per 32-lane half, and a half holds two frame groups whose rows, 16 x 271
-// floats apart, start 48 banks apart: 8 of each group's 16 bank pairs are the
-// other's (2-way, and the row pitch cannot change).  Measured so:
-// SQ_LDS_BANK_CONFLICT per window 440 -> 936, array cycles up, fp32 +0.1 %
-// over the tables alone (noise), bf16 -2.4 %; not kept.
+// per 32-lane half, and a half holds two frame groups whose rows (then 16 x
+// 271 floats apart) started 48 banks apart: 8 of each group's 16 bank pairs
+// were the other's (2-way).  Measured so: SQ_LDS_BANK_CONFLICT per window
+// 440 -> 936, array cycles up, fp32 +0.1 % over the tables alone (noise),
+// bf16 -2.4 %; not kept.  (At today's 8 x 270 floats the rows again start 48
+// banks apart.)
 template <bool MODE_B, typename PF>
-__device__ __forceinline__ void fe_rest(f2 (&a)[16], int j, float* __restrict__ row, float* __restrict__ xs,
-                                        const FeTables& tb, int esp_pack, const PF& pf WK_SP_PARAM) {
+__device__ __forceinline__ void fe_rest(f2 (&a)[16], int j, float* __restrict__ row, const FeTables& tb, int esp_pack,
+                                        const PF& pf WK_SP_PARAM) {
   pf(0);
   dft16(a);  // slot s: A[s ^ (j & 8)] at a[dft16_out(s)]
   WK_FE_HIT(2);
 
   // twiddle W256^(n2 k1), n2 = j, k1 = s ^ (j & 8); each half is twiddled
   // just before it is written (fewer live registers)
-  f2* x2 = reinterpret_cast<f2*>(xs);
+  f2* x2 = reinterpret_cast<f2*>(row);
   const int wb = fe_lds::xpose_wr(j);
   // slots s0, s0 + 1: one 16-byte read of the lane's twiddle row feeds both products
   auto tw2 = [&](int s0, f2& b0, f2& b1) {
@@ -610,7 +616,7 @@ __device__ __forceinline__ void cmvn_lane2(float& v0, float& v1, bool valid, int
 }
 
 // LDS carve (floats; fe_lds::carve): twiddle rows [16 lanes][52] | log-mel
-// [40][64] | power rows [63][271] | window rows [16 lanes][20].  The standalone
+// [40][64] | power rows [63][270] | window rows [16 lanes][20].  The standalone
 // front-end stops before the window (it reads the window from the constant
 // table: kFeLdsNoWin keeps two workgroups per CU); the fused kernel copies it
 // to LDS.
@@ -625,8 +631,9 @@ static_assert(kFeLdsNoWin * 4 <= fe_lds::kStandaloneLimitBytes, "standalone fron
 static_assert(kLOff % 4 == 0, "log-mel rows are read with ds_read_b128");
 static_assert(kTabOff % 4 == 0 && fe_lds::kRowPitch % 4 == 0 && kWinOff % 4 == 0 && fe_lds::kWinPitch % 4 == 0,
               "table rows are read with ds_read_b128 (the carve's base is 16-byte aligned)");
-static_assert(kPOff % 2 == 0 && kPRow % 2 == 1 && kPRow >= fe_lds::kXposeFloats + 1,
-              "row f's transpose scratch is row + (f & 1): 8-byte aligned, 270 floats");
+static_assert(kPOff % 2 == 0 && kPRow % 2 == 0 && kPRow >= fe_lds::kXposeFloats && kPRow >= 258,
+              "a power row is 8-byte aligned: it is its own transpose scratch and the mel reads it as pairs of bins");
+static_assert(fe_lds::mel_rows_conflict_free(kPRow), "lane-per-frame ds_read_b64: 32 lanes on 32 distinct bank pairs");
 
 // Fill the twiddle rows (and the window rows, WIN) of the LDS carve (all threads of the WG).
 template <bool MODE_B, bool WIN>

@@ -47,13 +47,40 @@ constexpr int win_row_off(int j) { return j * kWinPitch; }
 constexpr int win_off(int j, int n1) { return win_row_off(j) + 2 * n1; }      // first of the pair
 constexpr int win_src(int j, int n1) { return 32 * n1 + 2 * j; }              // its index in the constant table
 
-// Transpose scratch inside the frame's power row (fe_rest), in f2 (8-byte)
-// units from the 8-byte aligned scratch base: writes at xpose_wr(j) + s,
+// Transpose scratch = the frame's power row (fe_rest), in f2 (8-byte) units
+// from the 8-byte aligned row base: writes at xpose_wr(j) + s,
 // reads of the diagonal half at xpose_rd(j, s), of the other at xpose_rd(j ^ 8, s).
 constexpr int kXposePitch = 17;
 constexpr int xpose_wr(int j) { return kXposePitch * (j & 7) + (j & 8); }
 constexpr int xpose_rd(int kc, int s) { return kc + kXposePitch * s; }
-constexpr int kXposeFloats = 2 * (kXposePitch * 7 + 15 + 1);   // 270
+constexpr int kXposeFloats = 2 * (kXposePitch * 7 + 15 + 1);   // 270 = the power row's pitch (wk_common.h kPRow)
+
+// Frame slots of the FFT phase (16 lanes per frame): lane group g of wave w
+// takes slot w + 8 (g & 1) + 16 r + 32 (g >> 1) in round r.  The two groups of
+// a 32-lane half are 8 rows apart, 8 x 270 = 16 mod 32 floats: their power-row
+// stores (ds_write_b32 / ds_write2_b32: bank = dword address mod 32, 16
+// consecutive banks per group) land on disjoint banks.  (16 rows apart, as
+// with the odd pitch 271, 16 x 270 = 0 mod 32: every store 2-way, which a
+// ds_write2_b32 pays for.)  Slot 0 is wave 0 / round 0 / group 0, slot 62
+// wave 6 / round 1 / group 3, the padding slot 63 wave 7 / round 1 / group 3:
+// the lanes the edge-frame paths of fe_stage0 assume.
+constexpr int kRoundSlots = 16;
+constexpr int slot_base(int g) { return 8 * (g & 1) + 32 * (g >> 1); }
+constexpr int frame_slot(int w, int r, int g) { return w + kRoundSlots * r + slot_base(g); }
+
+// The mel's lane-per-frame reads of the power rows, {p[2m], p[2m+1]} as one
+// ds_read_b64: served per 32-lane half, lane l at float address p_row * l + 2m.
+// Conflict-free when the 32 row bases of a half sit on 32 distinct bank pairs
+// (p_row even; 270 = 14 mod 64, and 7 l mod 32 is a bijection).
+constexpr bool mel_rows_conflict_free(int p_row) {
+  if (p_row % 2) return false;
+  for (int half = 0; half < 2; ++half) {
+    unsigned seen = 0;
+    for (int l = 32 * half; l < 32 * half + 32; ++l) seen |= 1u << ((p_row * l % 64) / 2);
+    if (seen != 0xffffffffu) return false;
+  }
+  return true;
+}
 
 static_assert(kRowPitch % 4 == 0 && (kRowPitch / 4) % 2 == 1 && kRowUsed <= kRowPitch,
               "twiddle rows: 16-byte aligned, 16 lanes on 16 distinct bank quads");

@@ -47,9 +47,9 @@ __global__ __launch_bounds__(kFeBlock, 4) void wk_frontend_kernel(const T* __res
 
   fe_init_tables<MODE_B, false>(smem, threadIdx.x, kFeBlock);
   const FeTables tb = fe_tables(smem, j, MODE_B ? kWinB : kWinA);   // window: constant table (L1-resident)
-  // Frame slots: groups 0/1 (and 2/3) of a wave take frames 16 apart so their
-  // pitch-17 transpose images fall in disjoint LDS banks.
-  const int slot_base = 16 * (g & 1) + 32 * (g >> 1);
+  // Frame slots: groups 0/1 (and 2/3) of a wave take frames 8 apart so their
+  // power-row stores fall in disjoint LDS banks (fe_lds::frame_slot).
+  const int slot_base = fe_lds::slot_base(g);
   __syncthreads();
 
   // Wave-round (unit u, round r) geometry: frame t (within the clip), local
@@ -60,7 +60,7 @@ __global__ __launch_bounds__(kFeBlock, 4) void wk_frontend_kernel(const T* __res
     xp = audio + clip * clip_stride;
     const int f0 = chunk * kNFramesB;
     nfc = min(kNFramesB, nf - f0);
-    fl = wave + 8 * r + slot_base;
+    fl = wave + fe_lds::kRoundSlots * r + slot_base;
     t = f0 + fl;
     slow = MODE_B && ((r == 0 && wave == 0) || (r == 1 && wave == 6));   // holds frame 0 or 62
   };
@@ -96,7 +96,7 @@ __global__ __launch_bounds__(kFeBlock, 4) void wk_frontend_kernel(const T* __res
       }
       // pf is consumed: prefetch the next wave-round, (u,1) or (u+grid,0), into it.
       prefetch(r == 0 ? u : u + gridDim.x, r ^ 1, pf);
-      if (fl < nfc) fe_rest<MODE_B>(a, j, P + fl * kPRow, P + fl * kPRow + (fl & 1), tb, esp_pack, NoPrefetch());
+      if (fl < nfc) fe_rest<MODE_B>(a, j, P + fl * kPRow, tb, esp_pack, NoPrefetch());
     }
     wg_barrier_lds();
 

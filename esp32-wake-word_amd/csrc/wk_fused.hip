@@ -113,8 +113,8 @@ static_assert(kF1Off % 4 == 0 && kF2Off % 4 == 0 && kB1Off % 2 == 0 && kB2Off % 
 enum { kConvF32 = 0, kConvBf16 = 1, kConvBf16x3 = 2 };
 // Scratch power row for the one frame slot past the clip (frame 63): its lanes
 // still run the FFT so that the prefetch loads issued inside fe_rest execute.
-constexpr int kDummyRowOff = (kImgEnd + 1) & ~1;          // even: its scratch is row + (63 & 1)
-constexpr int kFusedLds = kDummyRowOff + kPRow + 1;
+constexpr int kDummyRowOff = (kImgEnd + 1) & ~1;          // even: the row is its own 8-byte aligned scratch
+constexpr int kFusedLds = kDummyRowOff + kPRow;
 static_assert(kFusedLds * 4 <= 163840, "fused LDS budget");
 // The CNN role writes only inside [kGOff, kImgEnd) (pooled features,
 // classifier partials, the second log-mel buffer it reads, control words,
@@ -256,7 +256,7 @@ __device__ __forceinline__ void fe_role(float* smem, const T* __restrict__ audio
   unsigned* ctrl = reinterpret_cast<unsigned*>(smem + kCtrlOff);
   const int g = lane >> 4, j = lane & 15;
   const FeTables tb = fe_tables(smem, j, nullptr);   // window and twiddle rows of lane j, both in LDS
-  const int slot_base = 16 * (g & 1) + 32 * (g >> 1);
+  const int slot_base = fe_lds::slot_base(g);
   // frame slot of this wave (moving the edge frames to other waves measured neutral), its rounds r0..r1
   const int fw = FEW == 8 || wave < 8 ? wave : wave - 4;
   const int r0 = FEW == 8 || wave < 8 ? 0 : 1, r1 = FEW == 8 || wave < 4 ? 1 : r0;
@@ -266,9 +266,10 @@ __device__ __forceinline__ void fe_role(float* smem, const T* __restrict__ audio
   unsigned gen = 0, p_wait = 0;
 
   // Static frame assignment: wave w, round r, lane group g takes frame
-  // w + 8r + 16(g&1) + 32(g>>1) (groups 0/1 16 frames apart: disjoint LDS
-  // banks).  A dynamic hand-out through an LDS counter was measured slower:
-  // the atomic's return latency lands on the prefetch path.  Both edge
+  // w + 8(g&1) + 16r + 32(g>>1) (fe_lds::frame_slot; groups 0/1 8 frames
+  // apart: 8 x 270 = 16 mod 32 floats, disjoint LDS banks for the stores).
+  // A dynamic hand-out through an LDS counter was measured slower: the
+  // atomic's return latency lands on the prefetch path.  Both edge
   // frames in wave 0's round 0 (when an edge round still issued 21 per-lane
   // reflected loads: one such round per clip instead of two) measured -1 %:
   // that wave then finishes last at the clip barrier.
@@ -305,7 +306,7 @@ __device__ __forceinline__ void fe_role(float* smem, const T* __restrict__ audio
   // plain mapping (profiles/edge_rows_ab.md).  Bit-identical either way.
   auto fwr = [&](int r) { return FEW == 8 && WK_FE_ROUND1_SWAP && r == 1 ? fw ^ 4 : fw; };
   auto pf_ctx = [&](const T* p, bool ok, int r) -> PfCtx {
-    const int fl = fwr(r) + 8 * r + slot_base;
+    const int fl = fwr(r) + fe_lds::kRoundSlots * r + slot_base;
     return {make_rsrc(p, ok ? kClipBytes : 0u), 256 * fl - 160, fl == 0 ? 160 : 256 * fl - 161};
   };
 
@@ -319,7 +320,7 @@ __device__ __forceinline__ void fe_role(float* smem, const T* __restrict__ audio
   for (int64_t i = 0; i < n_mine; ++i) {
 #pragma unroll 1
     for (int r = r0; r <= r1; ++r) {
-      const int fl = fwr(r) + 8 * r + slot_base;   // == frame index t (one chunk per clip)
+      const int fl = fwr(r) + fe_lds::kRoundSlots * r + slot_base;   // == frame index t (one chunk per clip)
       const int edge = r == 0 && fwr(r) == 0 ? 1 : r == 1 && fwr(r) == 6 ? 2 : 0;   // frame 0 / 62 in this wave-round
       f2 a[16];
 #ifdef WK_DIAG
@@ -346,17 +347,16 @@ __device__ __forceinline__ void fe_role(float* smem, const T* __restrict__ audio
       };
       WK_STAMP(1);
       float* row = fl < kNFramesB ? P + fl * kPRow : smem + kDummyRowOff;
-      fe_rest<true>(a, j, row, row + (fl & 1), tb, 0, pf_part WK_SP_ARG);
+      fe_rest<true>(a, j, row, tb, 0, pf_part WK_SP_ARG);
     }
     role_sync<kPrioFe, FEW>(ctrl, kCtrlFeBar, gen, lane);               // all power rows of clip i written
     WK_STAMP(7);
     if (mel_wave && i >= 2 && !(diag & 1)) spin_until_all8<kPrioFe>(ctrl, kCtrlLFree, (unsigned)(i - 1));   // clip i-2's DCT done
     WK_STAMP(10);
     if (mel_wave) {
-      // The row base stays opaque (one VGPR with kPOff in it), so the mel's
-      // power reads take bin offsets as read2 immediates; folded into the
-      // immediates, kPOff pushed them past read2's 255-dword reach and every
-      // pair of reads cost a v_add_u32 for its address.
+      // The row base stays opaque (one VGPR with kPOff in it, 8-byte aligned:
+      // kPOff and kPRow are even), so the mel's ds_read_b64 of bin pairs take
+      // their offsets as immediates from one address register.
       int prow = kPOff + min(lane, kNFramesB - 1) * kPRow;
       asm volatile("" : "+v"(prow));
       mel_dispatch<true>(melw, smem + prow, (i & 1 ? L1 : L) + lane);
@@ -401,14 +401,20 @@ __device__ __forceinline__ void dct_cmvn_clip(const float* __restrict__ lbuf, in
                                               uint16_t* __restrict__ B0, uint16_t* __restrict__ X0,
                                               float* __restrict__ fo, int lane) {
   const int li = lane & 15, lk = lane >> 4;
-  // A fragments kDctB16[li][4 s + lk], re-read (L1/L2-resident, 2.5 KB) per
-  // clip: kept live across the batch they pushed the fp32 CNN into spills.
-  int aoff = 4 * (li * 40 + lk);
+  // A fragments dct[li][4 s + lk], s = 0..9: this lane's row of kDctB16
+  // (lane-major, wk_tables.h), three 16-byte loads, re-read (L1/L2-resident,
+  // 3 KB) per clip: kept live across the batch they pushed the fp32 CNN into
+  // spills.
+  int aoff = 48 * lane;
   asm volatile("" : "+v"(aoff));   // not loop-invariant: keep the loads here
   const auto ra = make_rsrc(kDctB16, sizeof(kDctB16));
-  float dA[10];
+  float dA[12];
 #pragma unroll
-  for (int s = 0; s < 10; ++s) dA[s] = buf_load(ra, aoff, 16 * s);
+  for (int s = 0; s < 12; s += 4) {
+    const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ra, aoff, 4 * s, 0));
+#pragma unroll
+    for (int r = 0; r < 4; ++r) dA[s + r] = v[r];
+  }
   f32x4 d[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
 #pragma unroll
   for (int s = 0; s < 10; ++s) {
@@ -506,21 +512,28 @@ __device__ __forceinline__ void cnn_role(float* base, const float* __restrict__ 
   const int li = lane & 15, lk = lane >> 4;
   unsigned gen = 0;
   const auto rs = make_rsrc(pk, 4 * kNumPacked);
-  const int lv = 4 * lane;
 
-  // Weights come fragment-major (wk_kernels.h pack_fragments): one coalesced
-  // 256-byte load per A fragment.  conv3's (48 fragments) stay in VGPRs; the
-  // other layers' are re-read from L2 per batch.
+  // Weights come fragment-major, four k-steps per lane contiguous (wk_kernels.h
+  // pack_fragments, frag_idx): one coalesced 16-byte-per-lane load per four A
+  // fragments.  conv3's (48 fragments) stay in VGPRs; the other layers' are
+  // re-read from L2 per batch.
+  auto load_frags = [&](auto& w, int first) {   // w[s] = this lane's value of the fragment first + 64 s
+    constexpr int n = sizeof(w) / sizeof(float);
+    static_assert(n % 4 == 0, "whole groups of four k-steps");
+#pragma unroll
+    for (int s = 0; s < n; s += 4) {
+      const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, 16 * lane, 4 * (first + s * 64), 0));
+#pragma unroll
+      for (int r = 0; r < 4; ++r) w[s + r] = v[r];
+    }
+  };
   float w3[48];
   s8 w3b[6];
   if constexpr (BF || X3) {
 #pragma unroll
     for (int s = 0; s < 6; ++s) w3b[s] = frag_bf(kPbW3 + (cw * 6 + s) * kBfFrag);
   }
-  if constexpr (CM == kConvF32) {
-#pragma unroll
-    for (int s = 0; s < 48; ++s) w3[s] = buf_load(rs, lv, 4 * (kPkW3 + (cw * 48 + s) * 64));
-  }
+  if constexpr (CM == kConvF32) load_frags(w3, kPkW3 + cw * 48 * 64);
   const int64_t n_batches = (n_mine + NBF - 1) / NBF;
   src.init(cw, lane);
   bool eager_done = false;
@@ -603,10 +616,7 @@ __device__ __forceinline__ void cnn_role(float* base, const float* __restrict__ 
 #pragma unroll
       for (int s = 0; s < 2; ++s) w1l[s] = frag_bf(kLoW + kPbW1 + ((cw & 1) * 2 + s) * kBfFrag);
     }
-    if constexpr (CM == kConvF32) {
-#pragma unroll
-      for (int s = 0; s < 12; ++s) w1[s] = buf_load(rs, lv, 4 * (kPkW1 + ((cw & 1) * 12 + s) * 64));
-    }
+    if constexpr (CM == kConvF32) load_frags(w1, kPkW1 + (cw & 1) * 12 * 64);
     WK_STAMP(0);
     role_sync<0>(ctrl, kCtrlCnnBar, gen, lane);   // conv1 image complete (and the previous batch's partials)
     if (b > 0) fc2(b - 1);
@@ -682,8 +692,7 @@ __device__ __forceinline__ void cnn_role(float* base, const float* __restrict__ 
       }
     } else {
       float w2[24];
-#pragma unroll
-      for (int s = 0; s < 24; ++s) w2[s] = buf_load(rs, lv, 4 * (kPkW2 + ((cw & 3) * 24 + s) * 64));
+      load_frags(w2, kPkW2 + (cw & 3) * 24 * 64);
       const int co0 = 16 * (cw & 3);
 #pragma unroll 1
       for (int p = 0; p < 2; ++p) {
@@ -734,10 +743,7 @@ __device__ __forceinline__ void cnn_role(float* base, const float* __restrict__ 
       }
     }
     float wf1[16];
-    {
-#pragma unroll
-      for (int s = 0; s < 16; ++s) wf1[s] = buf_load(rs, lv, 4 * (kPkF1 + (cw * 16 + s) * 64));
-    }
+    load_frags(wf1, kPkF1 + cw * 16 * 64);
     WK_STAMP(5);
     role_sync<0>(ctrl, kCtrlCnnBar, gen, lane);
     try_eager(b);

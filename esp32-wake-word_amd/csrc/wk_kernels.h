@@ -100,19 +100,24 @@ constexpr int kNumWeights = kOffF2 + 64;        // 40224
 
 // Fragment-major copy of the weights for the MFMA kernels.  Per 16-row output
 // tile and k-step, the 64 values lane l feeds as the A operand of
-// v_mfma_f32_16x16x4_f32 (row = l&15), so a wave loads one fragment with one
-// coalesced 256-byte load.
+// v_mfma_f32_16x16x4_f32 (row = l&15).  Within a tile the k-steps go in groups
+// of four, lane-major inside a group (frag_idx): lane l's values of steps
+// 4 i .. 4 i + 3 are contiguous and 16-byte aligned, so a wave loads four
+// fragments with one coalesced 1 KiB load (buffer_load_dwordx4; fragment by
+// fragment it was four 256-byte buffer_load_dword).
 //   conv ([clip][t][ci] images): step s = 4 (tap * CB + cb) + j, lane group
 //     q = l>>4 feeds ci = 16 cb + 4 q + j at that tap (Cin padded to 16);
 //     taps 0 and 2 are g0, g2, tap 1 the Winograd tap G1 = (g0 + g1 + g2) / 2.
 //   classifier.0 (v_mfma_f32_4x4x1_16b_f32, 16 blocks): wave w, step s feeds
 //     k = 16 w + s; lane l is the output row o = l.
-constexpr int kPkW1 = 0;                        // [2 tiles][12 s][64]
-constexpr int kPkW2 = kPkW1 + 2 * 12 * 64;      // [4][24][64]
-constexpr int kPkW3 = kPkW2 + 4 * 24 * 64;      // [8][48][64]
-constexpr int kPkF1 = kPkW3 + 8 * 48 * 64;      // [8 waves][16 s][64 o]  (k = 16 w + s)
+constexpr int kPkW1 = 0;                        // [2 tiles][12 s / 4][64][4]
+constexpr int kPkW2 = kPkW1 + 2 * 12 * 64;      // [4][24 / 4][64][4]
+constexpr int kPkW3 = kPkW2 + 4 * 24 * 64;      // [8][48 / 4][64][4]
+constexpr int kPkF1 = kPkW3 + 8 * 48 * 64;      // [8 waves][16 s / 4][64 o][4]  (k = 16 w + s)
 constexpr int kPkF2 = kPkF1 + 8 * 16 * 64;      // [64]
 constexpr int kNumPacked = kPkF2 + 64;
+// Float offset, inside a tensor's block, of lane l's value of step s of tile t (nsteps a multiple of 4).
+constexpr int frag_idx(int nsteps, int t, int s, int l) { return (t * nsteps + (s & ~3)) * 64 + 4 * l + (s & 3); }
 
 // bf16 variant (WK_PREC_BF16 / BF16X3, v_mfma_f32_16x16x32_bf16): per 16-row
 // tile and k-step s, lane l feeds 8 consecutive k = 32s + 8(l>>4) + j (j = 0..7)
@@ -161,7 +166,7 @@ inline void pack_fragments_bf16(const float* w, uint16_t* pk, bool lo = false) {
 // Host-side packing of the WK_NUM_WEIGHTS blob into the fragment-major layouts.
 inline void pack_fragments(const float* w, float* pk) {
   auto conv_blocked = [&](int off, int tiles, int cin, int cin_pad, int wbase) {
-    const int cb_n = cin_pad / 16, nsteps = 12 * cb_n;
+    const int cb_n = cin_pad / 16, nsteps = 12 * cb_n;   // a multiple of 4
     for (int t = 0; t < tiles; ++t)
       for (int s = 0; s < nsteps; ++s)
         for (int l = 0; l < 64; ++l) {
@@ -174,7 +179,7 @@ inline void pack_fragments(const float* w, float* pk) {
             // kernel forms G2 = (g0 + g2) - G1 (conv_wino_v)
             v = tap == 1 ? (float)(0.5 * ((double)g[0] + (double)g[1] + (double)g[2])) : g[tap];
           }
-          pk[off + (t * nsteps + s) * 64 + l] = v;
+          pk[off + frag_idx(nsteps, t, s, l)] = v;
         }
   };
   conv_blocked(kPkW1, 2, 13, 16, kOffW1);
@@ -182,7 +187,7 @@ inline void pack_fragments(const float* w, float* pk) {
   conv_blocked(kPkW3, 8, 64, 64, kOffW3);
   for (int wv = 0; wv < 8; ++wv)
     for (int s = 0; s < 16; ++s)
-      for (int o = 0; o < 64; ++o) pk[kPkF1 + (wv * 16 + s) * 64 + o] = w[kOffF1 + o * 128 + 16 * wv + s];
+      for (int o = 0; o < 64; ++o) pk[kPkF1 + frag_idx(16, wv, s, o)] = w[kOffF1 + o * 128 + 16 * wv + s];
   for (int o = 0; o < 64; ++o) pk[kPkF2 + o] = w[kOffF2 + o];
 }
 

@@ -35,7 +35,7 @@ constexpr int kFrameLead = 162;   // a frame unit's resource starts this many sa
                                   // frame fl of the unit is at base 256*fl + 2 (even, like 256t - 160)
 
 // Frame slot of lane group g of wave `wave` in round r (wk_frontend_kernel's).
-__device__ __forceinline__ int scan_slot(int wave, int r, int g) { return wave + 8 * r + 16 * (g & 1) + 32 * (g >> 1); }
+__device__ __forceinline__ int scan_slot(int wave, int r, int g) { return fe_lds::frame_slot(wave, r, g); }
 
 template <typename T>
 __global__ __launch_bounds__(kFeBlock, 4) void wk_scan_frames_kernel(const T* __restrict__ audio, int64_t rec_stride,
@@ -92,7 +92,7 @@ __global__ __launch_bounds__(kFeBlock, 4) void wk_scan_frames_kernel(const T* __
       if (fl < nfc) fe_stage0<true>(pf, 256 * fl + 2, 0, j, false, tb, a);
       // pf is consumed: prefetch the next wave-round, (u,1) or (u+grid,0), into it.
       prefetch(r == 0 ? u : u + gridDim.x, r ^ 1, pf);
-      if (fl < nfc) fe_rest<true>(a, j, P + fl * kPRow, P + fl * kPRow + (fl & 1), tb, 0, NoPrefetch());
+      if (fl < nfc) fe_rest<true>(a, j, P + fl * kPRow, tb, 0, NoPrefetch());
     }
     wg_barrier_lds();
 
@@ -156,7 +156,7 @@ __global__ __launch_bounds__(kFeBlock, 4) void wk_scan_assemble_kernel(const T* 
         load_raw<true>(rs, base, j, kWinSamples, true, true, raw, (e >> 1) * hop);
         f2 a[16];
         fe_stage0<true>(raw, base, kWinSamples, j, true, tb, a);
-        fe_rest<true>(a, j, P + e * kPRow, P + e * kPRow + (e & 1), tb, 0, NoPrefetch());
+        fe_rest<true>(a, j, P + e * kPRow, tb, 0, NoPrefetch());
       }
     }
     wg_barrier_lds();

@@ -156,26 +156,44 @@ def partition(fb: np.ndarray, n_parts: int, weights=None):
 
 
 def emit_mel(fb: np.ndarray, name: str, mode: str, scale: float):
-    """One straight-line function per wave: P row -> log-mel row."""
+    """One straight-line function per wave: P row -> log-mel row.  The row is
+    read in aligned pairs {p[2m], p[2m+1]}, one 8-byte LDS load each (the row
+    pitch is even, wk_common.h kPRow): a wave whose range starts or ends on an
+    odd bin reads the straddling pair and uses one half.  All of a wave's reads
+    (at most 27) are issued first, into the register image p[] of its bins,
+    then the FMAs run, per filter over its bins in ascending order; the
+    scheduling barriers keep that order, so each step waits only for the reads
+    it consumes.  (Reads issued 4, 8, 16 ahead of their FMAs instead: fp32
+    -1.0 %, -0.6 %, +0.4 % against the parent, all of them first +1.3 %;
+    profiles/power_pitch_ab.md.)"""
     env = os.environ.get("WK_MEL_WEIGHTS")
     bounds, worst = partition(fb, N_WAVES, [float(v) for v in env.split(",")] if env else MEL_WAVE_WEIGHTS)
     lines = [f"// {name}: filters per wave {bounds}, worst-wave cost {worst:.4g}"]
+    n_reads = []
     for w, (a, b) in enumerate(bounds):
-        lines.append(f"__device__ __forceinline__ void {name}_w{w}(const float* __restrict__ p, float* __restrict__ l) {{")
+        lines.append(f"__device__ __forceinline__ void {name}_w{w}(const float* __restrict__ row, float* __restrict__ l) {{")
+        lines.append("  const wk_mel_lds_f2* q = (const wk_mel_lds_f2*)__builtin_assume_aligned(row, 8);")
         for m in range(a, b):
             lines.append(f"  float a{m} = 0.0f;")
         bins = sorted(set(int(k) for m in range(a, b) for k in np.nonzero(fb[:, m])[0]))
+        pairs = sorted(set(k // 2 for k in bins))
+        n_reads.append(len(pairs))
+        lines.append(f"  float p[{2 * pairs[-1] + 2}];   // bins of this wave, in registers (constant indices)")
+        for pr in pairs:
+            halves = "".join(f" p[{k}] = r{pr}.{h};" for h, k in (("x", 2 * pr), ("y", 2 * pr + 1)) if k in bins)
+            lines.append(f"  const wk_mel_f2 r{pr} = q[{pr}];{halves}")
         for k in bins:
             terms = [(m, fb[k, m]) for m in range(a, b) if fb[k, m] != 0.0]
             lines.append(f"  {{ const float v = p[{k}];" +
                          "".join(f" a{m} = __builtin_fmaf(v, {f32(np.float32(wt) * np.float32(scale))}, a{m});"
-                                 for m, wt in terms) + " }")
+                                 for m, wt in terms) + " } __builtin_amdgcn_sched_barrier(0);")
         for m in range(a, b):
             if mode == "B":
                 lines.append(f"  l[{m} * WK_LSTRIDE] = wk::wk_logf(a{m} + 1e-6f);")
             else:
                 lines.append(f"  l[{m} * WK_LSTRIDE] = wk::wk_logf(__builtin_fmaxf(a{m}, 1e-12f));")
         lines.append("}")
+    lines.insert(1, f"// {name}: 8-byte power reads per wave {n_reads}, {sum(n_reads)} in all")
     lines.append(f"template <int W> __device__ __forceinline__ void {name}_wave(const float* p, float* l);")
     for w in range(N_WAVES):
         lines.append(f"template <> __device__ __forceinline__ void {name}_wave<{w}>(const float* p, float* l) {{ {name}_w{w}(p, l); }}")
@@ -201,6 +219,14 @@ def main():
     out.append("__constant__ float kWinB[320] = {" + ", ".join(f32(v) for v in wB * sgn) + "};")
     out.append("__constant__ float kWinA[320] = {" + ", ".join(f32(v) for v in wA * sgn) + "};")
     out.append("")
+    # The mel functions read a frame's power row, in LDS, two bins at a time.
+    # Volatile loads through an LDS-address-space pointer stay single
+    # ds_read_b64 (2 LDS-array cycles per wave; plain loads are merged into
+    # ds_read2_b64 or split into ds_read2_b32, 8 and 4 cycles for the same bytes).
+    out.append("// a frame's power row in LDS, read as aligned pairs of bins: single 8-byte loads (see emit_mel)")
+    out.append("typedef float wk_mel_f2 __attribute__((ext_vector_type(2)));")
+    out.append("typedef volatile __attribute__((address_space(3))) wk_mel_f2 wk_mel_lds_f2;")
+    out.append("")
     # Mode B: P holds |U|^2 with U = 2 V  ->  fold the 1/4 into the weights (exact).
     out.append(emit_mel(fbB, "melB", "B", 0.25))
     out.append("")
@@ -214,10 +240,16 @@ def main():
         scale = math.sqrt(1.0 / N_MELS) if c == 0 else math.sqrt(2.0 / N_MELS)
         body = " ".join(f"s = __builtin_fmaf(l[{m} * WK_LSTRIDE], {f32(dA[c, m])}, s);" for m in range(N_MELS))
         out.append(f"__device__ __forceinline__ float dctA_{c}(const float* __restrict__ l) {{ float s = 0.0f; {body} return {f32(scale)} * s; }}")
-    # Mode B DCT as the A operand of a 16x40 fp32 MFMA GEMM (rows 13-15 zero).
+    # Mode B DCT as the A operand of a 16x40 fp32 MFMA GEMM (rows 13-15 zero),
+    # lane-major: lane 16 lk + li holds its ten K-step values dB16[li][4 s + lk],
+    # s = 0..9, contiguous (padded to 12 floats: three 16-byte loads per lane).
     dB16 = np.zeros((16, N_MELS), np.float32)
     dB16[:N_MFCC] = dB
-    out.append("__constant__ float kDctB16[16 * 40] = {" + ", ".join(f32(v) for v in dB16.reshape(-1)) + "};")
+    lanes = np.zeros((64, 12), np.float32)
+    for lane in range(64):
+        lanes[lane, :10] = [dB16[lane & 15, 4 * s + (lane >> 4)] for s in range(10)]
+    out.append("__constant__ __attribute__((aligned(16))) float kDctB16[64 * 12] = {" +
+               ", ".join(f32(v) for v in lanes.reshape(-1)) + "};")
     out.append("template <bool MODE_B> __device__ __forceinline__ float dct_coef(int c, const float* __restrict__ l) {")
     out.append("  switch (c) {")
     for c in range(N_MFCC):
