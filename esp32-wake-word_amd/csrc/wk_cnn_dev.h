@@ -1,6 +1,6 @@
 // wk_cnn_dev.h -- device helpers of the xiaoa CNN (LightweightKWS,
-// ml_models/src/wakeModel.py:4-34) on the matrix cores, used by the CNN role of
-// wk_fused.hip (the fused kernel and the standalone CNN kernel).
+// ml_models/src/wakeModel.py:4-34) on the matrix cores, used by the CNN role
+// (wk_fused_cnn_role.h) of the fused kernel and of the standalone CNN kernel.
 //
 //   conv(13->32,k3,p1) ReLU maxpool2 -> conv(32->64) ReLU pool -> conv(64->128)
 //   ReLU pool -> mean over time -> Linear(128,64) ReLU -> Linear(64,1)
@@ -58,7 +58,7 @@ __device__ __forceinline__ void epi_gap(const f32x4& acc, float* __restrict__ g,
 // corrupted in lanes 48-63 beside it on the same SIMD.  The bf16-family fused
 // unit (wk_fused_xdl.hip) therefore runs its front-end in scalar fp32, and
 // tests/test_isa_rules.py checks every kernel of the library.  Diagnostic
-// one-unit builds (WK_FUSED_ONE_TU: packed front-end in every precision) issue
+// one-unit builds (WK_FUSED_ONE_TU: every precision in wk_fused.hip, packed front-end) issue
 // the step as two CDNA3-era v_mfma_f32_16x16x16_bf16 instead.
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short s8 __attribute__((ext_vector_type(8)));   // one lane's A or B fragment: 8 bf16 bit patterns

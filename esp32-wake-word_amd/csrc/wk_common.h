@@ -17,9 +17,9 @@ constexpr int kFeBlock = 512;        // 8 waves per front-end workgroup
 // complex arithmetic then compiles to packed fp32 VALU (v_pk_add/mul/fma_f32,
 // two lanes' worth of fp32 per issue), swaps and sign flips folded into the
 // op_sel / neg modifiers.
-// Diagnostic builds (and -DWK_FE_PACKED_ALL, the A/B baseline) compile the
-// whole fused kernel in one translation unit (wk_fused.hip), with the packed
-// front-end in every precision.
+// Diagnostic builds (and -DWK_FE_PACKED_ALL, the A/B baseline) instantiate
+// every precision of the fused kernel (wk_fused_dev.h) in one translation unit
+// (wk_fused.hip), with the packed front-end in every precision.
 #if defined(WK_DIAG) || defined(WK_FE_PACKED_ALL)
 #define WK_FUSED_ONE_TU 1
 #else
@@ -30,11 +30,13 @@ constexpr int kFeBlock = 512;        // 8 waves per front-end workgroup
 // The fused kernel's bf16-family unit (wk_fused_xdl.hip): the same complex
 // arithmetic as scalar fp32 pairs (v_fma/v_add/v_mul_f32; swaps and signs are
 // register choices and VOP3 neg modifiers), no packed ops -- beside the bf16
-// MFMAs those issue faster (wk_fused.hip header).
+// MFMAs those issue faster (wk_fused_dev.h header).  WK_FUSED_TU marks the two
+// fused units (wk_fused_lds.h defines it).
 // WK_FE_STAGED marks this unit wherever the two units' front-end schedules
 // differ, each measured in its own unit: the real-FFT split
 // issued stage by stage across each group of chains and the prefetch
-// placement (wk_fe_dev.h fe_rest), the round-1 frame slots (wk_fused.hip).
+// placement (wk_fe_dev.h fe_rest), the round-1 frame slots
+// (wk_fused_fe_role.h).
 #define WK_FE_STAGED 1
 struct __attribute__((aligned(8))) f2 {
   float x, y;

@@ -1,5 +1,6 @@
 // wk_fe_dev.h -- device code of the MFCC front-end (shared by the standalone
-// front-end kernel, wk_frontend.hip, and the fused kernel, wk_fused.hip).
+// front-end kernel, wk_frontend.hip, and the fused kernel's front-end role,
+// wk_fused_fe_role.h).
 // See wk_frontend.hip for the algorithm and the reference citations.
 #pragma once
 #include "wk_common.h"

@@ -1,9 +1,23 @@
-// wk_fused_xdl.hip -- the fused kernel for the bf16-family convolutions
-// (conv_mode 1 = bf16, config 4; 2 = split bf16): wk_fused.hip compiled again
-// with the front-end's complex arithmetic as scalar fp32 pairs (WK_FE_SCALAR,
+// wk_fused_xdl.hip -- the bf16-family unit of the fused kernel
+// (wk_fused_dev.h; conv_mode 1 = bf16, config 4; 2 = split bf16), with the
+// front-end's complex arithmetic as scalar fp32 pairs (WK_FE_SCALAR,
 // wk_common.h).  It defines wk::launch_fused_xdl only; wk::launch_fused
 // (wk_fused.hip) calls it for those modes.  Empty in diagnostic builds
 // (WK_FUSED_ONE_TU).
 #define WK_FE_SCALAR 1
-#define WK_FUSED_XDL_TU 1
-#include "wk_fused.hip"
+#include "wk_fused_dev.h"
+
+#if !WK_FUSED_ONE_TU
+namespace wk {
+
+hipError_t launch_fused_xdl(bool i16, const void* audio, int64_t batch, int64_t clip_stride, const float* w,
+                            const uint16_t* wbf, int conv_mode, float* logits, float* feats_or_null, int grid_cap,
+                            hipStream_t stream, unsigned* err, int diag) {
+  if (batch == 0) return hipSuccess;
+  if (conv_mode != kConvF32 && !wbf) return hipErrorInvalidValue;
+  return launch_fused_modes<kConvBf16x3, kConvBf16>(i16, conv_mode, audio, batch, clip_stride, w, wbf, logits,
+                                                    feats_or_null, grid_cap, stream, err, diag);
+}
+
+}  // namespace wk
+#endif

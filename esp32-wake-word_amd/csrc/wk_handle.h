@@ -40,7 +40,7 @@ struct wk_handle {
 
 namespace wk {
 
-// Convolution arithmetic of the fused kernels (wk_fused.hip kConvF32 / kConvBf16 / kConvBf16x3).
+// Convolution arithmetic of the fused kernels (wk_fused_lds.h kConvF32 / kConvBf16 / kConvBf16x3).
 inline int conv_mode_of(const wk_handle* h) {
   return h->cfg.precision == WK_PREC_BF16 ? 1 : (h->cfg.precision == WK_PREC_BF16X3 ? 2 : 0);
 }

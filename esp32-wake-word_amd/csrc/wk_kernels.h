@@ -34,7 +34,8 @@ hipError_t launch_frontend(bool mode_b, bool i16, const void* audio, int64_t bat
                            int64_t clip_stride, float* out, int esp_pack, int cmvn, int grid_cap,
                            float pre_emphasis, hipStream_t stream);   // pre_emphasis: 0.97 (mfcc.c:445), 0 = none
 
-// Fused front-end + CNN (wk_fused.hip), mode B only.
+// Fused front-end + CNN (kernel: wk_fused_dev.h; fp32 unit and this launcher:
+// wk_fused.hip), mode B only.
 // w = fp32 fragment-major weights (pack_fragments); wbf = bf16 conv fragments
 // (pack_fragments_bf16; hi then lo parts for split bf16) for conv_mode 1
 // (bf16, config 4) and 2 (split bf16, WK_PREC_BF16X3); conv_mode 0 = fp32 MFMA.
@@ -45,13 +46,14 @@ hipError_t launch_fused(bool i16, const void* audio, int64_t batch, int64_t clip
                                          // 2 = CNN role only; wrong logits
 
 // The bf16-family half of launch_fused (wk_fused_xdl.hip: conv_mode 1 / 2,
-// scalar-fp32 front-end); launch_fused calls it.
+// scalar-fp32 front-end); launch_fused calls it.  Not defined in diagnostic
+// one-unit builds (WK_FUSED_ONE_TU, wk_common.h).
 hipError_t launch_fused_xdl(bool i16, const void* audio, int64_t batch, int64_t clip_stride, const float* w,
                             const uint16_t* wbf, int conv_mode, float* logits, float* feats_or_null, int grid_cap,
                             hipStream_t stream, unsigned* err, int diag);
 
-// CNN on caller features (wk_fused.hip, the fused kernel's CNN role fed from
-// HBM): feats [B][13][63] -> logits [B]; conv_mode as launch_fused.
+// CNN on caller features (wk_fused.hip: the fused kernel's CNN role,
+// wk_fused_cnn_role.h, fed from HBM): feats [B][13][63] -> logits [B]; conv_mode as launch_fused.
 hipError_t launch_cnn_fused(const float* feats, int64_t batch, const float* w, const uint16_t* wbf, int conv_mode,
                             float* logits, int grid_cap, hipStream_t stream, unsigned* err);
 

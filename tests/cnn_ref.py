@@ -63,7 +63,7 @@ def weight_set(name):
 
 
 # ---- batch sizes ------------------------------------------------------------
-# launch_fused (wk_fused.hip): grid = min(B, n_cu) workgroups; workgroup w takes
+# launch_fused (wk_fused.hip; launch_fused_as, wk_fused_dev.h): grid = min(B, n_cu) workgroups; workgroup w takes
 # clips w, w + grid, ... (n_mine = (B - 1 - w) / grid + 1) in batches of NBF = 4.
 # With C = n_cu, 4C + 1 gives workgroup 0 a second batch of nv = 1 beside
 # single-batch workgroups; 5C + 3: nv = 2 (w < 3) and 1; 6C + C/2: nv = 3 and 2;

@@ -283,10 +283,10 @@ def test_table_reads_are_16_byte_reads_in_the_shipped_isa(tmp_path):
 
 
 def test_fused_carve_within_budget():
-    """The fused kernel's whole carve is a static_assert in wk_fused.hip; here: the
+    """The fused kernel's whole carve is a static_assert in wk_fused_lds.h; here: the
     device header derives its offsets from the layout header's carve()."""
     with open(os.path.join(CSRC, "wk_fe_dev.h")) as fh:
         dev = fh.read()
     assert "fe_lds::carve(WK_LSTRIDE, kNFramesB, kPRow)" in dev
-    with open(os.path.join(CSRC, "wk_fused.hip")) as fh:
+    with open(os.path.join(CSRC, "wk_fused_lds.h")) as fh:
         assert "static_assert(kFusedLds * 4 <= 163840" in fh.read()

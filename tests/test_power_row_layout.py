@@ -137,10 +137,11 @@ def test_fused_budget_and_alignment_asserts_are_in_place():
     with open(os.path.join(CSRC, "wk_fe_dev.h")) as fh:
         dev = fh.read()
     assert "kPRow % 2 == 0" in dev and "fe_lds::mel_rows_conflict_free(kPRow)" in dev
-    with open(os.path.join(CSRC, "wk_fused.hip")) as fh:
-        fused = fh.read()
-    assert "static_assert(kFusedLds * 4 <= 163840" in fused
-    assert "fe_lds::slot_base(g)" in fused and "fe_lds::kRoundSlots * r" in fused
+    with open(os.path.join(CSRC, "wk_fused_lds.h")) as fh:
+        assert "static_assert(kFusedLds * 4 <= 163840" in fh.read()
+    with open(os.path.join(CSRC, "wk_fused_fe_role.h")) as fh:
+        fe_role = fh.read()
+    assert "fe_lds::slot_base(g)" in fe_role and "fe_lds::kRoundSlots * r" in fe_role
 
 
 def mel_functions(text: str, name: str):
