@@ -13,87 +13,100 @@ constexpr int kPRow = 270;           // LDS pitch of one frame's power row = the
                                      // 32 lane-per-frame reads of a half on 32 distinct bank pairs
 constexpr int kFeBlock = 512;        // 8 waves per front-end workgroup
 
-// Complex values live in VGPR pairs as float2 {re, im}: the front-end's
-// complex arithmetic then compiles to packed fp32 VALU (v_pk_add/mul/fma_f32,
-// two lanes' worth of fp32 per issue), swaps and sign flips folded into the
-// op_sel / neg modifiers.
-// Diagnostic builds (and -DWK_FE_PACKED_ALL, the A/B baseline) instantiate
-// every precision of the fused kernel (wk_fused_dev.h) in one translation unit
-// (wk_fused.hip), with the packed front-end in every precision.
-#if defined(WK_DIAG) || defined(WK_FE_PACKED_ALL)
-#define WK_FUSED_ONE_TU 1
-#else
-#define WK_FUSED_ONE_TU 0
-#endif
-
-#if defined(WK_FE_SCALAR) && defined(WK_FUSED_TU)
-// The fused kernel's bf16-family unit (wk_fused_xdl.hip): the same complex
-// arithmetic as scalar fp32 pairs (v_fma/v_add/v_mul_f32; swaps and signs are
-// register choices and VOP3 neg modifiers), no packed ops -- beside the bf16
-// MFMAs those issue faster (wk_fused_dev.h header).  WK_FUSED_TU marks the two
-// fused units (wk_fused_lds.h defines it).
-// WK_FE_STAGED marks this unit wherever the two units' front-end schedules
-// differ, each measured in its own unit: the real-FFT split
-// issued stage by stage across each group of chains and the prefetch
-// placement (wk_fe_dev.h fe_rest), the round-1 frame slots
-// (wk_fused_fe_role.h).
-#define WK_FE_STAGED 1
-struct __attribute__((aligned(8))) f2 {
+// Complex values live in VGPR pairs {re, im}, in one of two types with the
+// same operations (each its own overloads below; the helpers that are the
+// same text for both are templates on the type):
+//   f2   a float2 vector: the complex arithmetic compiles to packed fp32 VALU
+//        (v_pk_add/mul/fma_f32, two lanes' worth of fp32 per issue), swaps
+//        and sign flips folded into the op_sel / neg modifiers.  Every kernel
+//        outside the fused kernel's bf16 family uses it.
+//   f2s  a pair of scalars: the same arithmetic as scalar fp32
+//        (v_fma/v_add/v_mul_f32; swaps and signs are register choices and
+//        VOP3 neg modifiers), no packed ops.
+typedef float f2 __attribute__((ext_vector_type(2)));
+struct __attribute__((aligned(8))) f2s {
   float x, y;
 };
-__device__ __forceinline__ f2 operator+(f2 a, f2 b) { return {a.x + b.x, a.y + b.y}; }
-__device__ __forceinline__ f2 operator-(f2 a, f2 b) { return {a.x - b.x, a.y - b.y}; }
-__device__ __forceinline__ f2 operator*(f2 a, f2 b) { return {a.x * b.x, a.y * b.y}; }
-__device__ __forceinline__ f2 operator-(f2 a) { return {-a.x, -a.y}; }
-__device__ __forceinline__ f2& operator+=(f2& a, f2 b) { return a = a + b; }
-__device__ __forceinline__ f2& operator-=(f2& a, f2 b) { return a = a - b; }
-__device__ __forceinline__ f2& operator*=(f2& a, f2 b) { return a = a * b; }
-__device__ __forceinline__ f2 swp(f2 a) { return {a.y, a.x}; }
-__device__ __forceinline__ f2 bx(f2 a) { return {a.x, a.x}; }
-__device__ __forceinline__ f2 by(f2 a) { return {a.y, a.y}; }
-__device__ __forceinline__ f2 fma2(f2 a, f2 b, f2 c) { return {__builtin_fmaf(a.x, b.x, c.x), __builtin_fmaf(a.y, b.y, c.y)}; }
-#else
-#define WK_FE_STAGED 0
-typedef float f2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ f2 swp(f2 a) { return __builtin_shufflevector(a, a, 1, 0); }
 __device__ __forceinline__ f2 bx(f2 a) { return __builtin_shufflevector(a, a, 0, 0); }
 __device__ __forceinline__ f2 by(f2 a) { return __builtin_shufflevector(a, a, 1, 1); }
 __device__ __forceinline__ f2 fma2(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
-#endif
-__device__ __forceinline__ f2 sub_ib(f2 a, f2 b) { return fma2(swp(b), f2{1.0f, -1.0f}, a); }  // a - i b
-__device__ __forceinline__ f2 add_ib(f2 a, f2 b) { return fma2(swp(b), f2{-1.0f, 1.0f}, a); }  // a + i b
 
-// a * w, w = {c, s} a runtime twiddle: v_pk_mul + one v_pk_fma whose second
-// operand is w swizzled to {-s, s} by op_sel/neg_lo (the compiler would
+__device__ __forceinline__ f2s operator+(f2s a, f2s b) { return {a.x + b.x, a.y + b.y}; }
+__device__ __forceinline__ f2s operator-(f2s a, f2s b) { return {a.x - b.x, a.y - b.y}; }
+__device__ __forceinline__ f2s operator*(f2s a, f2s b) { return {a.x * b.x, a.y * b.y}; }
+__device__ __forceinline__ f2s operator-(f2s a) { return {-a.x, -a.y}; }
+__device__ __forceinline__ f2s& operator+=(f2s& a, f2s b) { return a = a + b; }
+__device__ __forceinline__ f2s& operator-=(f2s& a, f2s b) { return a = a - b; }
+__device__ __forceinline__ f2s& operator*=(f2s& a, f2s b) { return a = a * b; }
+__device__ __forceinline__ f2s swp(f2s a) { return {a.y, a.x}; }
+__device__ __forceinline__ f2s bx(f2s a) { return {a.x, a.x}; }
+__device__ __forceinline__ f2s by(f2s a) { return {a.y, a.y}; }
+__device__ __forceinline__ f2s fma2(f2s a, f2s b, f2s c) { return {__builtin_fmaf(a.x, b.x, c.x), __builtin_fmaf(a.y, b.y, c.y)}; }
+
+// The front-end's arithmetic flavour: the complex type and the schedule
+// choices measured with it.  Helpers of wk_fe_dev.h take it as a template
+// parameter (default FePacked); the fused kernel (wk_fused_dev.h) picks it
+// from its conv mode, so every unit that instantiates a precision builds the
+// front-end that precision ships with.
+//
+// FePacked: the standalone kernels and the fused kernel beside the fp32
+// MFMAs, which share the fp32 datapath (scalar there: -2.8 %, DESIGN 5.1,
+// profiles/r05au_*).  Measured in the fp32 unit (wk_fused.hip): per-chain
+// order of the real-FFT split (staged: -0.1 %), front-loaded prefetch parts
+// issued one step earlier (+1.5 %, profiles/r06u..r06x), plain round-1 slots
+// (swap: +0.1 %, noise, profiles/edge_rows_ab.md).
+struct FePacked {
+  typedef f2 c2;
+  static constexpr bool staged = false, round1_swap = false;
+};
+// FeScalar: the fused kernel beside the bf16 MFMAs (wk_fused_xdl.hip), which
+// run on the matrix pipe: packed fp32 issues slower than scalar there (+4.8 %
+// bf16, profiles/r05au_*), and the K = 32 rule (wk_cnn_dev.h) forbids it.
+// Measured in that unit: the split issued stage by stage across each group of
+// chains with the later prefetch placement (staged, wk_fe_dev.h fe_rest: bf16
+// +0.8 %, profiles/r06m_staged_ab.txt), round 1's frame slots swapped between
+// waves w and w ^ 4 (round1_swap, wk_fused_fe_role.h: bf16 +1.5 %,
+// profiles/edge_rows_ab.md).  Either flag is bit-identical both ways, so an
+// A/B is a one-word edit here.
+struct FeScalar {
+  typedef f2s c2;
+  static constexpr bool staged = true, round1_swap = true;
+};
+
+template <typename C> __device__ __forceinline__ C sub_ib(C a, C b) { return fma2(swp(b), C{1.0f, -1.0f}, a); }  // a - i b
+template <typename C> __device__ __forceinline__ C add_ib(C a, C b) { return fma2(swp(b), C{-1.0f, 1.0f}, a); }  // a + i b
+
+// a * w, w = {c, s} a runtime twiddle.  Packed: v_pk_mul + one v_pk_fma whose
+// second operand is w swizzled to {-s, s} by op_sel/neg_lo (the compiler would
 // build that pair with two extra VALU ops).
 __device__ __forceinline__ f2 cmul2(f2 a, f2 w) {
-#if defined(WK_FE_SCALAR) && defined(WK_FUSED_TU)
-  return {__builtin_fmaf(-a.y, w.y, a.x * w.x), __builtin_fmaf(a.x, w.y, a.y * w.x)};
-#endif
   const f2 t = a * bx(w);
   f2 r;
   asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_lo:[0,1,0]" : "=v"(r) : "v"(a), "v"(w), "v"(t));
   return r;
 }
+__device__ __forceinline__ f2s cmul2(f2s a, f2s w) {
+  return {__builtin_fmaf(-a.y, w.y, a.x * w.x), __builtin_fmaf(a.x, w.y, a.y * w.x)};
+}
 // cmul2 in two phases, t = cmul2_a(a, w) then cmul2_b(a, w, t), for a group
-// of independent products issued phase by phase (WK_FE_STAGED): the same
+// of independent products issued phase by phase (FE::staged): the same
 // operations as cmul2, so the same bits.
-__device__ __forceinline__ f2 cmul2_a(f2 a, f2 w) { return a * bx(w); }
+template <typename C> __device__ __forceinline__ C cmul2_a(C a, C w) { return a * bx(w); }
 __device__ __forceinline__ f2 cmul2_b(f2 a, f2 w, f2 t) {
-#if defined(WK_FE_SCALAR) && defined(WK_FUSED_TU)
-  return {__builtin_fmaf(-a.y, w.y, t.x), __builtin_fmaf(a.x, w.y, t.y)};
-#else
   f2 r;
   asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_lo:[0,1,0]" : "=v"(r) : "v"(a), "v"(w), "v"(t));
   return r;
-#endif
+}
+__device__ __forceinline__ f2s cmul2_b(f2s a, f2s w, f2s t) {
+  return {__builtin_fmaf(-a.y, w.y, t.x), __builtin_fmaf(a.x, w.y, t.y)};
 }
 // a * w for a compile-time constant w.
-__device__ __forceinline__ f2 cmulc(f2 a, f2 w) { return fma2(swp(a), f2{-w.y, w.y}, a * f2{w.x, w.x}); }
+template <typename C> __device__ __forceinline__ C cmulc(C a, C w) { return fma2(swp(a), C{-w.y, w.y}, a * C{w.x, w.x}); }
 
 // W16^e = exp(-2*pi*i*e/16).
-__device__ __forceinline__ f2 w16(int e) {
+template <typename C> __device__ __forceinline__ C w16(int e) {
   constexpr float c8 = 0.92387953251128674f, s8 = 0.38268343236508978f, h = 0.70710678118654752f;
   switch (e & 15) {
     case 0: return {1.f, 0.f};
@@ -115,21 +128,21 @@ __device__ __forceinline__ f2 w16(int e) {
   }
 }
 
-__device__ __forceinline__ f2 swap_mul(f2 v, f2 s) { return swp(v) * s; }
+template <typename C> __device__ __forceinline__ C swap_mul(C v, C s) { return swp(v) * s; }
 // v * W16^e with the quarter turns folded (e is a constant after unrolling).
-__device__ __forceinline__ f2 twid16(f2 v, int e) {
+template <typename C> __device__ __forceinline__ C twid16(C v, int e) {
   switch (e & 15) {
     case 0: return v;
-    case 4: return swap_mul(v, f2{1.0f, -1.0f});    // -i v
+    case 4: return swap_mul(v, C{1.0f, -1.0f});    // -i v
     case 8: return -v;
-    case 12: return swap_mul(v, f2{-1.0f, 1.0f});   // i v
-    default: return cmulc(v, w16(e));
+    case 12: return swap_mul(v, C{-1.0f, 1.0f});   // i v
+    default: return cmulc(v, w16<C>(e));
   }
 }
 
 // In-place 4-point forward DFT (8 packed ops).
-__device__ __forceinline__ void dft4(f2& a0, f2& a1, f2& a2, f2& a3) {
-  const f2 t0 = a0 + a2, t1 = a0 - a2, t2 = a1 + a3, t3 = a1 - a3;
+template <typename C> __device__ __forceinline__ void dft4(C& a0, C& a1, C& a2, C& a3) {
+  const C t0 = a0 + a2, t1 = a0 - a2, t2 = a1 + a3, t3 = a1 - a3;
   a0 = t0 + t2;
   a2 = t0 - t2;
   a1 = sub_ib(t1, t3);
@@ -139,7 +152,7 @@ __device__ __forceinline__ void dft4(f2& a0, f2& a1, f2& a2, f2& a3) {
 // In-register 16-point forward DFT (radix 4x4).  Input a[n] natural order;
 // output A[k] lands in a[4*(k&3) + (k>>2)] (use dft16_out()).  Inputs known to
 // be zero at compile time fold away (built with -fno-signed-zeros).
-__device__ __forceinline__ void dft16(f2 (&a)[16]) {
+template <typename C> __device__ __forceinline__ void dft16(C (&a)[16]) {
 #pragma unroll
   for (int nb = 0; nb < 4; ++nb) dft4(a[nb], a[4 + nb], a[8 + nb], a[12 + nb]);
 #pragma unroll

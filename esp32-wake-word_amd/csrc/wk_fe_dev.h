@@ -9,20 +9,9 @@
 
 namespace wk {
 
-// W32^k2 = exp(-2*pi*i*k2/32), k2 = 0..8.
-__device__ __forceinline__ f2 w32(int k2) {
-  switch (k2) {
-    case 0: return {1.0f, 0.0f};
-    case 1: return {0.98078528040323043f, -0.19509032201612825f};
-    case 2: return {0.92387953251128674f, -0.38268343236508978f};
-    case 3: return {0.83146961230254524f, -0.55557023301960218f};
-    case 4: return {0.70710678118654752f, -0.70710678118654752f};
-    case 5: return {0.55557023301960218f, -0.83146961230254524f};
-    case 6: return {0.38268343236508978f, -0.92387953251128674f};
-    case 7: return {0.19509032201612825f, -0.98078528040323043f};
-    default: return {0.0f, -1.0f};
-  }
-}
+// The helpers the fused kernel shares with the standalone kernels take the
+// arithmetic flavour FE (FePacked / FeScalar, wk_common.h) or its complex type
+// C = FE::c2; FePacked is the default, which is what the standalone kernels run.
 
 // Raw samples of one frame-group slot, prefetched into registers one round
 // ahead (buffer loads: clip base in SGPRs, out-of-range reads return 0):
@@ -107,18 +96,19 @@ __device__ __forceinline__ void load_raw(__amdgpu_buffer_rsrc_t rs, int base, in
 // fe_stage0_rows takes them from there (the rows' own loads fall outside the
 // clip and return 0).  The one sample no row holds, x[160] for frame 0, comes
 // in xb (xb_idx; base - 1 for every other frame).
-// The packed unit front-loads the parts (rows 0-3, 4-6, 7-8, 9) and issues
-// them earlier in the round (fe_rest); the scalar unit issues rows 3k..3k+2.
+// The packed flavour front-loads the parts (rows 0-3, 4-6, 7-8, 9) and issues
+// them earlier in the round (fe_rest); the scalar flavour issues rows 3k..3k+2.
+template <typename FE = FePacked>
 __device__ __forceinline__ constexpr int pf_part(int n1) {
-  return WK_FE_STAGED ? n1 / 3 : (n1 < 4 ? 0 : n1 < 7 ? 1 : n1 < 9 ? 2 : 3);
+  return FE::staged ? n1 / 3 : (n1 < 4 ? 0 : n1 < 7 ? 1 : n1 < 9 ? 2 : 3);
 }
-template <typename T>
+template <typename FE = FePacked, typename T>
 __device__ __forceinline__ void load_raw_part(__amdgpu_buffer_rsrc_t rs, int base, int xb_idx, int j, Raw<T>& r,
                                               int part) {
   const int v0 = base + 2 * j;
 #pragma unroll
   for (int n1 = 0; n1 < 10; ++n1)
-    if (pf_part(n1) == part) raw_ld2<T>(rs, v0 + 32 * n1, r.x0[n1], r.x1[n1]);
+    if (pf_part<FE>(n1) == part) raw_ld2<T>(rs, v0 + 32 * n1, r.x0[n1], r.x1[n1]);
   if (part == 0) r.xb = raw_ld<T>(rs, xb_idx);
 }
 
@@ -158,8 +148,9 @@ struct FeTables {
 // roundings, different bits.  With this form every unit compiles to the same
 // floating-point operations as with the slot-major tables
 // (tests/test_gpu_fe_bits.py holds it to them).
-__device__ __forceinline__ void lds_pair16(const float* p, f2& a, f2& b) {
-  const f2* q = reinterpret_cast<const f2*>(__builtin_assume_aligned(p, 16));
+template <typename C>
+__device__ __forceinline__ void lds_pair16(const float* p, C& a, C& b) {
+  const C* q = reinterpret_cast<const C*>(__builtin_assume_aligned(p, 16));
   a = q[0];
   b = q[1];
 }
@@ -173,10 +164,11 @@ __device__ __forceinline__ void lds_pair16(const float* p, f2& a, f2& b) {
 __device__ __forceinline__ bool fe_split_flip(int j, int k2) {
   return j == 8 || (j >= 1 && j <= 7 && !(k2 & 1)) || (j >= 9 && (k2 & 1));
 }
-__device__ __forceinline__ f2 fe_split_tw(int j, int k2) {   // W512^(j + 16 k2), or -conj of it
+template <typename C = f2>
+__device__ __forceinline__ C fe_split_tw(int j, int k2) {   // W512^(j + 16 k2), or -conj of it
   float sn, cs;
   sincospif(-(float)(j + 16 * k2) / 256.0f, &sn, &cs);
-  return fe_split_flip(j, k2) ? f2{-cs, sn} : f2{cs, sn};
+  return fe_split_flip(j, k2) ? C{-cs, sn} : C{cs, sn};
 }
 
 // Stage 0: pre-emphasis + window of the 320 frame samples as 160 complex
@@ -261,9 +253,8 @@ template <int CTRL, int ROWS>
 __device__ __forceinline__ float dpp_rows(float old, float src) {   // rows outside ROWS, lanes without a source: old
   return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(src), CTRL, ROWS, 0xF, false));
 }
-template <int EDGE, typename T>
-__device__ __forceinline__ void fe_stage0_rows(const Raw<T>& raw, int lane, const f2 (&w)[10], f2 (&a)[16],
-                                               float pre) {
+template <int EDGE, typename T, typename C>
+__device__ __forceinline__ void fe_stage0_rows(const Raw<T>& raw, int lane, const C (&w)[10], C (&a)[16], float pre) {
   const int j = lane & 15;
   float prev_rot = 0.0f;
 #pragma unroll
@@ -304,15 +295,15 @@ __device__ __forceinline__ void fe_stage0_rows(const Raw<T>& raw, int lane, cons
     float y0 = __builtin_fmaf(pre, pm, c0);   // pre = -0.97
     const float y1 = __builtin_fmaf(pre, p1, c1);
     if (EDGE == 1 && n1 == 5) y0 = lane == 0 ? x0 : y0;   // y[0] = x[0]
-    a[n1] = f2{y0, y1} * w[n1];
+    a[n1] = C{y0, y1} * w[n1];
   }
 }
-template <typename T>
+template <typename T, typename C>
 __device__ __forceinline__ void fe_stage0_fused(const Raw<T>& raw, int lane, int edge, const FeTables& tb,
-                                                f2 (&a)[16], float pre = -0.97f) {
+                                                C (&a)[16], float pre = -0.97f) {
   // All ten window pairs are read up front (see fe_stage0): this lane's
   // window row, five 16-byte reads.
-  f2 w[10];
+  C w[10];
 #pragma unroll
   for (int n1 = 0; n1 < 10; n1 += 2) lds_pair16(tb.win + fe_lds::win_off(0, n1), w[n1], w[n1 + 1]);
   // The windowed pairs are formed in each branch, so the paths merge on a[]
@@ -321,11 +312,12 @@ __device__ __forceinline__ void fe_stage0_fused(const Raw<T>& raw, int lane, int
   else if (edge == 1) fe_stage0_rows<1>(raw, lane, w, a, pre);
   else fe_stage0_rows<2>(raw, lane, w, a, pre);
 #pragma unroll
-  for (int n1 = 10; n1 < 16; ++n1) a[n1] = f2{0.0f, 0.0f};
+  for (int n1 = 10; n1 < 16; ++n1) a[n1] = C{0.0f, 0.0f};
 }
 
 // Stages 1..4 of one frame -> its power row (bins 0..256) in LDS.  All
-// complex arithmetic is packed fp32 (see f2 in wk_common.h).
+// complex arithmetic is in FE's complex type (f2: packed fp32, f2s: scalar
+// pairs; wk_common.h).
 // The row (8-byte aligned, kPRow = 270 floats) is also the transpose scratch.
 // tb.row: this lane's twiddle row (W256 twiddles, then fe_split_tw(j, k2), k2 = 0..7).
 // pf(k), k = 0..3, is called at four points of the round (prefetch parts);
@@ -375,44 +367,45 @@ __device__ __forceinline__ void fe_stage0_fused(const Raw<T>& raw, int lane, int
 // 440 -> 936, array cycles up, fp32 +0.1 % over the tables alone (noise),
 // bf16 -2.4 %; not kept.  (At today's 8 x 270 floats the rows again start 48
 // banks apart.)
-template <bool MODE_B, typename PF>
-__device__ __forceinline__ void fe_rest(f2 (&a)[16], int j, float* __restrict__ row, const FeTables& tb, int esp_pack,
-                                        const PF& pf WK_SP_PARAM) {
+template <bool MODE_B, typename FE = FePacked, typename PF>
+__device__ __forceinline__ void fe_rest(typename FE::c2 (&a)[16], int j, float* __restrict__ row, const FeTables& tb,
+                                        int esp_pack, const PF& pf WK_SP_PARAM) {
+  typedef typename FE::c2 C;
   pf(0);
   dft16(a);  // slot s: A[s ^ (j & 8)] at a[dft16_out(s)]
   WK_FE_HIT(2);
 
   // twiddle W256^(n2 k1), n2 = j, k1 = s ^ (j & 8); each half is twiddled
   // just before it is written (fewer live registers)
-  f2* x2 = reinterpret_cast<f2*>(row);
+  C* x2 = reinterpret_cast<C*>(row);
   const int wb = fe_lds::xpose_wr(j);
   // slots s0, s0 + 1: one 16-byte read of the lane's twiddle row feeds both products
-  auto tw2 = [&](int s0, f2& b0, f2& b1) {
-    f2 wa, wc;
+  auto tw2 = [&](int s0, C& b0, C& b1) {
+    C wa, wc;
     lds_pair16(tb.row + fe_lds::tw_off(0, s0), wa, wc);
     b0 = cmul2(a[dft16_out(s0)], wa);
     b1 = cmul2(a[dft16_out(s0 + 1)], wc);
   };
-  f2 b[8];
-  if constexpr (!WK_FE_STAGED) pf(1);
+  C b[8];
+  if constexpr (!FE::staged) pf(1);
 #pragma unroll
   for (int s = 0; s < 8; s += 2) tw2(s, b[s], b[s + 1]);
   pf(-1);   // the first write into this frame's LDS row follows (fused kernel: wait until the row is free)
 #pragma unroll
   for (int s = 0; s < 8; ++s) x2[wb + s] = b[s];
   WK_FE_HIT(3);
-  if constexpr (WK_FE_STAGED) pf(1);
-  f2 c[16];
+  if constexpr (FE::staged) pf(1);
+  C c[16];
   wave_lds_sync();
 #pragma unroll
   for (int s = 0; s < 8; ++s) c[s] = x2[fe_lds::xpose_rd(j, s)];
-  // The packed unit issues prefetch parts 1-3 one step earlier than the
-  // scalar unit (part 1 before the twiddles, part 2 after these reads, part 3
+  // The packed flavour issues prefetch parts 1-3 one step earlier than the
+  // scalar one (part 1 before the twiddles, part 2 after these reads, part 3
   // before the second DFT16 rather than after it): the loads get ~1 k more
   // cycles to land before the next round needs them; with the front-loaded
   // parts, fp32 +1.5 % (profiles/r06u..r06x); the scalar unit
   // measured -0.5 to 0 % with the earlier parts 2-3.
-  if constexpr (!WK_FE_STAGED) pf(2);
+  if constexpr (!FE::staged) pf(2);
 #pragma unroll
   for (int s = 8; s < 16; s += 2) tw2(s, b[s - 8], b[s - 7]);
   wave_lds_sync();
@@ -424,7 +417,7 @@ __device__ __forceinline__ void fe_rest(f2 (&a)[16], int j, float* __restrict__ 
   wave_lds_sync();
   WK_FE_HIT(4);
 
-  if constexpr (WK_FE_STAGED) {
+  if constexpr (FE::staged) {
     pf(2);
     dft16(c);  // +-Z[j + 16*k2] at c[dft16_out(k2)]
     pf(3);
@@ -445,18 +438,18 @@ __device__ __forceinline__ void fe_rest(f2 (&a)[16], int j, float* __restrict__ 
   // value per (lane, k2), sign-adjusted by fe_split_tw: the second part of
   // the lane's twiddle row, read two entries at a time (wsp) by the first
   // group of chains that needs them.
-  f2 sc0 = {1.0f, 1.0f}, sc = {1.0f, 1.0f};
+  C sc0 = {1.0f, 1.0f}, sc = {1.0f, 1.0f};
   if constexpr (!MODE_B) {
     // mfcc.c:267 power = |X|^2 / n_fft + 1e-12 = |U|^2 / 2048 + 1e-12; the
     // esp-dsp dsps_cplx2reC_fc32 packing (mfcc.c:261) doubles bins 1..255
     // (x4 in power) and zeroes bin 256 (parity unpinned).
     const float e = esp_pack ? 4.0f / 2048.0f : 1.0f / 2048.0f;
-    sc = f2{e, e};
-    sc0 = esp_pack ? (j == 0 ? f2{1.0f / 2048.0f, 0.0f} : sc) : sc;  // j==0, k2==0: bins 0 and 256
+    sc = C{e, e};
+    sc0 = esp_pack ? (j == 0 ? C{1.0f / 2048.0f, 0.0f} : sc) : sc;  // j==0, k2==0: bins 0 and 256
   }
   {
     // bin 128 (k2 = 8, column 0): X[128] = conj Z[128], so |U|^2 = 4 |Z[128]|^2.
-    const f2 z = c[dft16_out(8)];
+    const C z = c[dft16_out(8)];
     float p128 = 4.0f * __builtin_fmaf(z.x, z.x, z.y * z.y);
     if constexpr (!MODE_B) p128 = __builtin_fmaf(p128, sc.x, 1e-12f);
     if (j == 0) row[128] = p128;
@@ -465,102 +458,99 @@ __device__ __forceinline__ void fe_rest(f2 (&a)[16], int j, float* __restrict__ 
   // time, stage by stage, so independent ops fill each other's latency
   // (left to itself the scheduler emitted them back to back, one chain at a
   // time, with s_nop between dependent v_pk ops).
-  // WK_FE_STAGED (the bf16-family unit's scalar front-end, wk_common.h) also
-  // issues the group's DPP moves and each chain stage across the group: the
+  // FE::staged (the bf16 family's scalar front-end, FeScalar in wk_common.h)
+  // also issues the group's DPP moves and each chain stage across the group: the
   // same operations per value, bit-identical, bf16 +0.8 % (profiles/
   // r06m_staged_ab.txt); the packed fp32 unit measured -0.1 % with it, so
   // it keeps the per-chain order.
   constexpr int G = 3;
-  f2 wsp[8];
+  C wsp[8];
 #pragma unroll
   for (int k0 = 0; k0 < 8; k0 += G) {
-    f2 S[G], D[G], pw[G];
+    C S[G], D[G], pw[G];
 #pragma unroll
     for (int q = 0; q < 8; q += 2)
       if (q / G * G == k0) lds_pair16(tb.row + fe_lds::split_off(0, q), wsp[q], wsp[q + 1]);
-#if WK_FE_STAGED
-    // the partners' row_mirror moves of the group first, then their row_shr
-    // moves (a DPP read of a VGPR written by the previous VALU op waits 2 states)
-    float mx[G], my[G];
+    if constexpr (FE::staged) {
+      // the partners' row_mirror moves of the group first, then their row_shr
+      // moves (a DPP read of a VGPR written by the previous VALU op waits 2 states)
+      float mx[G], my[G];
 #pragma unroll
-    for (int t = 0; t < G; ++t)
-      if (k0 + t <= 7) {
-        const f2 sv = c[dft16_out(15 - k0 - t)];
-        mx[t] = dpp<0x140>(sv.x);
-        my[t] = dpp<0x140>(sv.y);
+      for (int t = 0; t < G; ++t)
+        if (k0 + t <= 7) {
+          const C sv = c[dft16_out(15 - k0 - t)];
+          mx[t] = dpp<0x140>(sv.x);
+          my[t] = dpp<0x140>(sv.y);
+        }
+#pragma unroll
+      for (int t = 0; t < G; ++t) {
+        const int k2 = k0 + t;
+        if (k2 > 7) continue;
+        const C zk = c[dft16_out(k2)];
+        const C own = c[dft16_out((16 - k2) & 15)];
+        C zq;
+        zq.x = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(own.x), __float_as_int(mx[t]), 0x111, 0xF, 0xF, false));
+        zq.y = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(own.y), __float_as_int(my[t]), 0x111, 0xF, 0xF, false));
+        S[t] = fma2(zq, C{1.0f, -1.0f}, zk);
+        D[t] = fma2(zq, C{-1.0f, 1.0f}, zk);
+      }
+      // the G chains issued stage by stage (the same operations per value)
+      C wt[G], tt[G], bb[G], uvx[G], uvy[G], sq[G];
+#pragma unroll
+      for (int t = 0; t < G; ++t)
+        if (k0 + t <= 7) {
+          wt[t] = wsp[k0 + t];
+          tt[t] = cmul2_a(D[t], wt[t]);
+        }
+#pragma unroll
+      for (int t = 0; t < G; ++t)
+        if (k0 + t <= 7) bb[t] = cmul2_b(D[t], wt[t], tt[t]);
+#pragma unroll
+      for (int t = 0; t < G; ++t)
+        if (k0 + t <= 7) {
+          uvx[t] = fma2(by(bb[t]), C{1.0f, -1.0f}, bx(S[t]));
+          uvy[t] = fma2(bx(bb[t]), C{-1.0f, 1.0f}, by(S[t]));
+        }
+#pragma unroll
+      for (int t = 0; t < G; ++t)
+        if (k0 + t <= 7) sq[t] = uvy[t] * uvy[t];
+#pragma unroll
+      for (int t = 0; t < G; ++t) {
+        const int k2 = k0 + t;
+        if (k2 > 7) continue;
+        pw[t] = fma2(uvx[t], uvx[t], sq[t]);
+        if constexpr (!MODE_B) pw[t] = fma2(pw[t], k2 == 0 ? sc0 : sc, C{1e-12f, 1e-12f});
+      }
+    } else {
+#pragma unroll
+      for (int t = 0; t < G; ++t) {
+        const int k2 = k0 + t;
+        if (k2 > 7) continue;
+        const C zk = c[dft16_out(k2)];
+        const C sv = c[dft16_out(15 - k2)];
+        const C own = c[dft16_out((16 - k2) & 15)];
+        // row_mirror (lane j <- 15 - j), then row_shr:1 (lane j <- j - 1) with
+        // bound_ctrl off: lane 0 has no source and keeps `old` = its own
+        // partner register -- no lane select.
+        C zq;
+        zq.x = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(own.x), __float_as_int(dpp<0x140>(sv.x)),
+                                                          0x111, 0xF, 0xF, false));
+        zq.y = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(own.y), __float_as_int(dpp<0x140>(sv.y)),
+                                                          0x111, 0xF, 0xF, false));
+        S[t] = fma2(zq, C{1.0f, -1.0f}, zk);
+        D[t] = fma2(zq, C{-1.0f, 1.0f}, zk);
       }
 #pragma unroll
-    for (int t = 0; t < G; ++t) {
-      const int k2 = k0 + t;
-      if (k2 > 7) continue;
-      const f2 zk = c[dft16_out(k2)];
-      const f2 own = c[dft16_out((16 - k2) & 15)];
-      f2 zq;
-      zq.x = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(own.x), __float_as_int(mx[t]), 0x111, 0xF, 0xF, false));
-      zq.y = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(own.y), __float_as_int(my[t]), 0x111, 0xF, 0xF, false));
-      S[t] = fma2(zq, f2{1.0f, -1.0f}, zk);
-      D[t] = fma2(zq, f2{-1.0f, 1.0f}, zk);
-    }
-#else
-#pragma unroll
-    for (int t = 0; t < G; ++t) {
-      const int k2 = k0 + t;
-      if (k2 > 7) continue;
-      const f2 zk = c[dft16_out(k2)];
-      const f2 sv = c[dft16_out(15 - k2)];
-      const f2 own = c[dft16_out((16 - k2) & 15)];
-      // row_mirror (lane j <- 15 - j), then row_shr:1 (lane j <- j - 1) with
-      // bound_ctrl off: lane 0 has no source and keeps `old` = its own
-      // partner register -- no lane select.
-      f2 zq;
-      zq.x = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(own.x), __float_as_int(dpp<0x140>(sv.x)),
-                                                        0x111, 0xF, 0xF, false));
-      zq.y = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(own.y), __float_as_int(dpp<0x140>(sv.y)),
-                                                        0x111, 0xF, 0xF, false));
-      S[t] = fma2(zq, f2{1.0f, -1.0f}, zk);
-      D[t] = fma2(zq, f2{-1.0f, 1.0f}, zk);
-    }
-#endif
-#if WK_FE_STAGED
-    // the G chains issued stage by stage (the same operations per value)
-    f2 wt[G], tt[G], bb[G], uvx[G], uvy[G], sq[G];
-#pragma unroll
-    for (int t = 0; t < G; ++t)
-      if (k0 + t <= 7) {
-        wt[t] = wsp[k0 + t];
-        tt[t] = cmul2_a(D[t], wt[t]);
+      for (int t = 0; t < G; ++t) {
+        const int k2 = k0 + t;
+        if (k2 > 7) continue;
+        const C bb = cmul2(D[t], wsp[k2]);
+        const C uvx = fma2(by(bb), C{1.0f, -1.0f}, bx(S[t]));
+        const C uvy = fma2(bx(bb), C{-1.0f, 1.0f}, by(S[t]));
+        pw[t] = fma2(uvx, uvx, uvy * uvy);
+        if constexpr (!MODE_B) pw[t] = fma2(pw[t], k2 == 0 ? sc0 : sc, C{1e-12f, 1e-12f});
       }
-#pragma unroll
-    for (int t = 0; t < G; ++t)
-      if (k0 + t <= 7) bb[t] = cmul2_b(D[t], wt[t], tt[t]);
-#pragma unroll
-    for (int t = 0; t < G; ++t)
-      if (k0 + t <= 7) {
-        uvx[t] = fma2(by(bb[t]), f2{1.0f, -1.0f}, bx(S[t]));
-        uvy[t] = fma2(bx(bb[t]), f2{-1.0f, 1.0f}, by(S[t]));
-      }
-#pragma unroll
-    for (int t = 0; t < G; ++t)
-      if (k0 + t <= 7) sq[t] = uvy[t] * uvy[t];
-#pragma unroll
-    for (int t = 0; t < G; ++t) {
-      const int k2 = k0 + t;
-      if (k2 > 7) continue;
-      pw[t] = fma2(uvx[t], uvx[t], sq[t]);
-      if constexpr (!MODE_B) pw[t] = fma2(pw[t], k2 == 0 ? sc0 : sc, f2{1e-12f, 1e-12f});
     }
-#else
-#pragma unroll
-    for (int t = 0; t < G; ++t) {
-      const int k2 = k0 + t;
-      if (k2 > 7) continue;
-      const f2 bb = cmul2(D[t], wsp[k2]);
-      const f2 uvx = fma2(by(bb), f2{1.0f, -1.0f}, bx(S[t]));
-      const f2 uvy = fma2(bx(bb), f2{-1.0f, 1.0f}, by(S[t]));
-      pw[t] = fma2(uvx, uvx, uvy * uvy);
-      if constexpr (!MODE_B) pw[t] = fma2(pw[t], k2 == 0 ? sc0 : sc, f2{1e-12f, 1e-12f});
-    }
-#endif
     // the group's low bins first, then its high bins: same-base stores 16
     // dwords apart, back to back, which the compiler pairs into ds_write2_b32
 #pragma unroll
@@ -637,7 +627,10 @@ static_assert(kPOff % 2 == 0 && kPRow % 2 == 0 && kPRow >= fe_lds::kXposeFloats 
 static_assert(fe_lds::mel_rows_conflict_free(kPRow), "lane-per-frame ds_read_b64: 32 lanes on 32 distinct bank pairs");
 
 // Fill the twiddle rows (and the window rows, WIN) of the LDS carve (all threads of the WG).
-template <bool MODE_B, bool WIN>
+// FE: the split twiddles pass through the flavour's complex type, as the rest
+// of the kernel's arithmetic does (built in f2 inside a scalar kernel, the
+// same values came out as different device code).
+template <bool MODE_B, bool WIN, typename FE = FePacked>
 __device__ __forceinline__ void fe_init_tables(float* smem, int tid, int nthreads) {
   if (WIN)
     for (int i = tid; i < 320; i += nthreads) {
@@ -653,7 +646,7 @@ __device__ __forceinline__ void fe_init_tables(float* smem, int tid, int nthread
   }
   for (int i = tid; i < 8 * 16; i += nthreads) {
     const int k2 = i / 16, jj = i % 16;
-    const f2 w = fe_split_tw(jj, k2);
+    const typename FE::c2 w = fe_split_tw<typename FE::c2>(jj, k2);
     smem[kTabOff + fe_lds::split_off(jj, k2)] = w.x;
     smem[kTabOff + fe_lds::split_off(jj, k2) + 1] = w.y;
   }

@@ -2,8 +2,8 @@
 // front-end's complex arithmetic as packed fp32: wk::launch_fused, which hands
 // the bf16 family to wk_fused_xdl.hip, and the standalone CNN
 // (wk_cnn_fused_kernel, wk::launch_cnn_fused) in every precision.  Diagnostic
-// builds (WK_FUSED_ONE_TU, wk_common.h) keep every precision of the fused
-// kernel here, and -DWK_DIAG adds the phase stamps' global and its reader.
+// builds (-DWK_DIAG) keep every precision of the fused kernel here, each with
+// its product front-end, and add the phase stamps' global and its reader.
 #include "wk_fused_dev.h"
 
 namespace {
@@ -64,7 +64,7 @@ hipError_t launch_fused(bool i16, const void* audio, int64_t batch, int64_t clip
                         hipStream_t stream, unsigned* err, int diag) {
   if (batch == 0) return hipSuccess;
   if (conv_mode != kConvF32 && !wbf) return hipErrorInvalidValue;
-#if WK_FUSED_ONE_TU   // diagnostic builds: every precision here
+#ifdef WK_DIAG   // every precision here: the stamps' global is one device symbol
   return launch_fused_modes<kConvBf16, kConvBf16x3, kConvF32>(i16, conv_mode, audio, batch, clip_stride, w, wbf, logits,
                                                               feats_or_null, grid_cap, stream, err, diag);
 #else

@@ -17,20 +17,22 @@
 // waves per SIMD), and features never touch HBM: per clip the kernel reads
 // its 64,000 audio bytes and writes one 4-byte logit.
 //
-// Product builds include this header in two units, each of which instantiates
-// the kernel for its own precisions.  wk_fused.hip: the fp32 convolutions,
-// with the front-end's complex arithmetic as packed fp32 (v_pk_*_f32).
-// wk_fused_xdl.hip: the bf16 / bf16x3 convolutions, with the same front-end as
-// scalar fp32 pairs (WK_FE_SCALAR, wk_common.h).  Beside the
-// bf16 MFMAs, which run on the matrix pipe, packed fp32 issues slower than
-// scalar: +4.8 % bf16.  Beside the fp32 MFMAs, which share the fp32
-// datapath, scalar is 2.8 % slower (profiles/r05au_*).
-// Diagnostic builds (WK_FUSED_ONE_TU) keep every precision in wk_fused.hip.
+// The conv mode picks the front-end's arithmetic flavour (FE in the kernel;
+// FePacked / FeScalar, wk_common.h).  fp32 convolutions: complex arithmetic as
+// packed fp32 (v_pk_*_f32).  bf16 / bf16x3: the same front-end as scalar fp32 pairs.
+// Beside the bf16 MFMAs, which run on the matrix pipe, packed fp32 issues
+// slower than scalar: +4.8 % bf16.  Beside the fp32 MFMAs, which share the
+// fp32 datapath, scalar is 2.8 % slower (profiles/r05au_*).
+// Product builds include this header in two units that compile in parallel,
+// wk_fused.hip (fp32) and wk_fused_xdl.hip (the bf16 family); diagnostic
+// builds (-DWK_DIAG) keep every precision in wk_fused.hip, each with the
+// flavour it ships with.
 #pragma once
 #include "wk_fused_lds.h"
 #include "wk_fused_fe_role.h"
 #include "wk_fused_cnn_role.h"
 #include "wk_kernels.h"
+#include <type_traits>
 
 namespace {
 
@@ -48,7 +50,8 @@ __global__ __launch_bounds__(kFusedBlock, 4) void wk_fused_kernel(const T* __res
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  fe_init_tables<true, true>(smem, tid, kFusedBlock);
+  typedef std::conditional_t<CM == kConvF32, FePacked, FeScalar> FE;   // the precision's front-end flavour
+  fe_init_tables<true, true, FE>(smem, tid, kFusedBlock);
   for (int i = tid; i < kFusedLds - kGOff; i += kFusedBlock) smem[kGOff + i] = 0.0f;  // ctrl, guards, pads
   __syncthreads();
   const int64_t n_mine = batch > (int64_t)blockIdx.x ? (batch - 1 - blockIdx.x) / gridDim.x + 1 : 0;
@@ -57,7 +60,7 @@ __global__ __launch_bounds__(kFusedBlock, 4) void wk_fused_kernel(const T* __res
   // front-end) measured -13 %.
   if (wave < kFeWaves) __builtin_amdgcn_s_setprio(kPrioFe);
   if (wave < kFeWaves) {
-    if (!(diag & 2)) fe_role<T>(smem, audio, n_mine, clip_stride, wave, lane, diag);
+    if (!(diag & 2)) fe_role<T, FE>(smem, audio, n_mine, clip_stride, wave, lane, diag);
   } else {
     if (!(diag & 1)) {
       LogmelSrc<CM, FEATS> src = {smem, reinterpret_cast<unsigned*>(smem + kCtrlOff), feats_out, (int64_t)blockIdx.x,

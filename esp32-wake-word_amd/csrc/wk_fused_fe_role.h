@@ -4,24 +4,18 @@
 // wk_fe_dev.h clip after clip and write each clip's log-mel image [40][63]
 // into one of two LDS buffers, which the CNN role (wk_fused_cnn_role.h) takes
 // from there.  The role is VALU + LDS bound and the kernel's critical path.
-// The complex arithmetic is packed fp32 in the fp32 unit and scalar fp32 pairs
-// in the bf16-family unit (f2, wk_common.h): the role's text is the same.
+// The complex arithmetic is packed fp32 beside the fp32 convolutions and
+// scalar fp32 pairs beside the bf16 family (the flavour FE: FePacked /
+// FeScalar, wk_common.h): the role's text is the same.
 #pragma once
 #include "wk_fused_lds.h"
 
 namespace {
 
-// Round-1 frame slots swapped between waves w and w ^ 4 (fe_role).  The
-// default is each unit's measured choice; -DWK_FE_ROUND1_SWAP=0/1 builds the
-// other one for an A/B (bit-identical either way).
-#ifndef WK_FE_ROUND1_SWAP
-#define WK_FE_ROUND1_SWAP WK_FE_STAGED
-#endif
-
 // ---------------------------------------------------------------------------
 // Front-end role (waves 0-7): mode B (torchaudio + CMVN), one clip at a time.
 // ---------------------------------------------------------------------------
-template <typename T>
+template <typename T, typename FE>
 __device__ __forceinline__ void fe_role(float* smem, const T* __restrict__ audio, int64_t n_mine,
                                         int64_t clip_stride, int wave, int lane, int diag) {
   float* P = smem + kPOff;
@@ -66,7 +60,7 @@ __device__ __forceinline__ void fe_role(float* smem, const T* __restrict__ audio
     int xb;     // the sample before it; frame 0: x[160], the one reflected sample no row holds
   };
   // Frame slot of round r (the wave's own, moving the edge frames to other
-  // waves measured neutral).  The bf16-family unit (scalar front-end) swaps
+  // waves measured neutral).  The scalar flavour (FE::round1_swap) swaps
   // round 1's slots between waves w and w ^ 4, so its second edge frame (62)
   // runs on wave 2 rather than wave 6: waves 4-7 issue after 0-3 on each SIMD
   // and reach the power-row barrier last.  Tuned when wave 6's edge round
@@ -74,7 +68,7 @@ __device__ __forceinline__ void fe_role(float* smem, const T* __restrict__ audio
   // profiles/r06ae_round1_swap_ab.txt) and re-measured with the short edge
   // rounds: bf16 still +1.5 % with the swap, fp32 +0.1 % (noise) and keeps the
   // plain mapping (profiles/edge_rows_ab.md).  Bit-identical either way.
-  auto fwr = [&](int r) { return WK_FE_ROUND1_SWAP && r == 1 ? wave ^ 4 : wave; };
+  auto fwr = [&](int r) { return FE::round1_swap && r == 1 ? wave ^ 4 : wave; };
   auto pf_ctx = [&](const T* p, bool ok, int r) -> PfCtx {
     const int fl = fwr(r) + fe_lds::kRoundSlots * r + slot_base;
     return {make_rsrc(p, ok ? kClipBytes : 0u), 256 * fl - 160, fl == 0 ? 160 : 256 * fl - 161};
@@ -84,7 +78,7 @@ __device__ __forceinline__ void fe_role(float* smem, const T* __restrict__ audio
   {
     const PfCtx c0 = pf_ctx(cptr, n_mine > 0, 0);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) load_raw_part(c0.rs, c0.base, c0.xb, j, pf, k);
+    for (int k = 0; k < 4; ++k) load_raw_part<FE>(c0.rs, c0.base, c0.xb, j, pf, k);
   }
   WK_STAMP_INIT
   for (int64_t i = 0; i < n_mine; ++i) {
@@ -92,7 +86,7 @@ __device__ __forceinline__ void fe_role(float* smem, const T* __restrict__ audio
     for (int r = 0; r <= 1; ++r) {
       const int fl = fwr(r) + fe_lds::kRoundSlots * r + slot_base;   // == frame index t (one chunk per clip)
       const int edge = r == 0 && fwr(r) == 0 ? 1 : r == 1 && fwr(r) == 6 ? 2 : 0;   // frame 0 / 62 in this wave-round
-      f2 a[16];
+      typename FE::c2 a[16];
 #ifdef WK_DIAG
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // diagnostic: time the wait for the prefetched audio apart
       WK_STAMP(11);
@@ -109,7 +103,7 @@ __device__ __forceinline__ void fe_role(float* smem, const T* __restrict__ audio
       // the first DFT16 overlap the slower waves' mel.
       auto pf_part = [&](int k) {
         if (k >= 0) {
-          load_raw_part(nx.rs, nx.base, nx.xb, j, pf, k);
+          load_raw_part<FE>(nx.rs, nx.base, nx.xb, j, pf, k);
         } else if (r == 0) {
           spin_until<kPrioFe>(ctrl, kCtrlFeBar, p_wait);
           WK_STAMP(9);
@@ -117,7 +111,7 @@ __device__ __forceinline__ void fe_role(float* smem, const T* __restrict__ audio
       };
       WK_STAMP(1);
       float* row = fl < kNFramesB ? P + fl * kPRow : smem + kDummyRowOff;
-      fe_rest<true>(a, j, row, tb, 0, pf_part WK_SP_ARG);
+      fe_rest<true, FE>(a, j, row, tb, 0, pf_part WK_SP_ARG);
     }
     role_sync<kPrioFe>(ctrl, kCtrlFeBar, gen, lane);               // all power rows of clip i written
     WK_STAMP(7);

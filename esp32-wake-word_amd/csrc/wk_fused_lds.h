@@ -1,16 +1,14 @@
 // wk_fused_lds.h -- what the two roles of the fused kernel share: the LDS
 // carve, the control words, the protocol on them (role barriers, the log-mel
 // hand-off, bounded spins and the abort report) and the diagnostic stamps.
-// Included by the two fused units only (wk_fused.hip, wk_fused_xdl.hip), first
-// of all: it marks the unit as a fused one for wk_common.h, and like the rest
-// of the wk_fused_* headers it keeps its names in the unit's unnamed namespace
+// Included by the two fused units only (wk_fused.hip, wk_fused_xdl.hip): like
+// the rest of the wk_fused_* headers it keeps its names in the unit's unnamed namespace
 // at global scope (the kernels' symbol names are looked up by tools and tests).
 //
 // The roles share no s_barrier: each synchronises its own 8 waves through an
 // LDS counter barrier, and the hand-off is two LDS counters (log-mel ready /
 // log-mel buffer free).
 #pragma once
-#define WK_FUSED_TU   // (wk_common.h: WK_FE_SCALAR applies to the fused translation units only)
 #include "wk_fe_dev.h"
 
 using namespace wk;

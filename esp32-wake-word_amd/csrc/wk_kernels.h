@@ -47,7 +47,7 @@ hipError_t launch_fused(bool i16, const void* audio, int64_t batch, int64_t clip
 
 // The bf16-family half of launch_fused (wk_fused_xdl.hip: conv_mode 1 / 2,
 // scalar-fp32 front-end); launch_fused calls it.  Not defined in diagnostic
-// one-unit builds (WK_FUSED_ONE_TU, wk_common.h).
+// builds (-DWK_DIAG: every precision in wk_fused.hip).
 hipError_t launch_fused_xdl(bool i16, const void* audio, int64_t batch, int64_t clip_stride, const float* w,
                             const uint16_t* wbf, int conv_mode, float* logits, float* feats_or_null, int grid_cap,
                             hipStream_t stream, unsigned* err, int diag);

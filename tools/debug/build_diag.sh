@@ -12,4 +12,7 @@ rm -f build/diag/*.o
 for f in $SRCS; do $HIPCC $FL -c csrc/$f -o build/diag/${f%.*}.o & done; wait
 for f in $SRCS; do [ -f build/diag/${f%.*}.o ] || { echo "compile of $f failed"; exit 1; }; done
 $HIPCC --offload-arch=gfx950 -shared -fPIC build/diag/*.o -Wl,-rpath,/opt/rocm/lib -o build/diag/libwakeword_diag.so
+# The K = 32 rule on what was built, as tests/test_isa_rules.py checks the product.
+# (tools/isa_rules.py: kernel_stats, k32_violations; prints its per-kernel table, exits 1 on a violation)
+python "$R/tools/isa_rules.py" build/diag/libwakeword_diag.so
 echo "$R/esp32-wake-word_amd/build/diag/libwakeword_diag.so"
