@@ -10,7 +10,9 @@
 // This unit holds no kernel: the handle (weights uploaded in each kernel's
 // layout by its unit's packer), the workspaces, stage timing, and the stage
 // sequence of wk_ctc_features / wk_ctc_forward / wk_ctc_transcribe, which
-// call the launchers declared in wk_ctc_dev.h.
+// call the launchers declared in wk_ctc_dev.h; and, for training, the fp32
+// forward that keeps its activations (wk_ctc_forward_train) and the entry to
+// the backward pass of wk_ctc_bwd.hip (wk_ctc_backward).
 #include <stdlib.h>
 #include <string.h>
 
@@ -64,6 +66,15 @@ struct wk_ctc {
   size_t tr_rows, tr_batch, tr_slots;
   int64_t last_batch;   // geometry of the last wk_ctc_forward (wk_ctc_frame_argmax)
   int32_t last_T;
+  // training (fp32 handles; wk_ctc_forward_train / wk_ctc_backward): W_hh as the backward's GEMM operand
+  // ([2 dir][384][128]) and as ctc_gru_bptt_kernel's W_hh^T fragments, and a workspace apart from the
+  // inference one (grown on demand): what the forward saves, then the backward's scratch
+  DevBuf<float> whh[2], whht_pk[2];
+  size_t tn_rows;
+  DevBuf<float> tn_feats, tn_x0, tn_gi[2], tn_y[2], tn_logits;
+  DevBuf<float> tn_hprev, tn_dya, tn_dyb, tn_gh, tn_dai, tn_dah, tn_coef, tn_pre, tn_t0, tn_t1, tn_part;
+  int64_t tn_batch;     // geometry of the last wk_ctc_forward_train (wk_ctc_backward)
+  int32_t tn_T;
   // stage timing (wk_ctc_profile): events recorded around each stage on the
   // call's stream, folded into per-stage sums when read or when the ring fills
   int prof;
@@ -114,6 +125,36 @@ hipError_t alloc_ws(wk_ctc* c, size_t rows) {
     c->ws_rows = rows;
   } else {
     for (const WsBuf& b : ws_table(c)) b.buf->reset();
+  }
+  return e;
+}
+
+// The training workspace, sized like alloc_ws: rows = batch x T, floats per row.
+std::array<WsBuf, 18> tn_table(wk_ctc* c) {
+  const size_t F = sizeof(float), H = kH;
+  return {{
+      {&c->tn_feats, F * kMels, true},   {&c->tn_x0, F * H, true},        {&c->tn_gi[0], F * 6 * H, true},
+      {&c->tn_gi[1], F * 6 * H, true},   {&c->tn_y[0], F * 2 * H, true},  {&c->tn_y[1], F * 2 * H, true},
+      {&c->tn_logits, F * (size_t)c->cfg.vocab, true},                    {&c->tn_hprev, F * 2 * H, true},
+      {&c->tn_dya, F * 2 * H, true},     {&c->tn_dyb, F * 2 * H, true},   {&c->tn_gh, F * 6 * H, true},
+      {&c->tn_dai, F * 6 * H, true},     {&c->tn_dah, F * 6 * H, true},   {&c->tn_coef, F * 10 * H, true},
+      {&c->tn_pre, F * H, true},         {&c->tn_t0, F * H, true},        {&c->tn_t1, F * H, true},
+      {&c->tn_part, 0, true},            // (the split-K partials: sized by ctc_bwd_part_floats)
+  }};
+}
+
+hipError_t alloc_tn(wk_ctc* c, size_t rows) {
+  c->tn_rows = 0;
+  c->tn_batch = 0;
+  for (const WsBuf& b : tn_table(c)) b.buf->reset();
+  hipError_t e = hipSuccess;
+  for (const WsBuf& b : tn_table(c))
+    if (e == hipSuccess)
+      e = b.buf->alloc_bytes(b.row_bytes ? b.row_bytes * rows : sizeof(float) * ctc_bwd_part_floats(c->cfg.vocab, (int64_t)rows));
+  if (e == hipSuccess) {
+    c->tn_rows = rows;
+  } else {
+    for (const WsBuf& b : tn_table(c)) b.buf->reset();
   }
   return e;
 }
@@ -229,6 +270,8 @@ wk_status wk_ctc_create(const wk_ctc_config* cfg, const float* w, wk_ctc** out) 
       if (e == hipSuccess) e = c->bih[l].upload(bih);
       if (e == hipSuccess) e = c->bhh[l].upload(bhh);
       if (e == hipSuccess) e = c->whh_pk[l].upload(ctc_pack_whh(whh.data()));
+      if (e == hipSuccess && !c->f16) e = c->whh[l].upload(whh);
+      if (e == hipSuccess && !c->f16) e = c->whht_pk[l].upload(ctc_pack_whht(whh.data()));
       if (e == hipSuccess && c->f16) e = upload_f16(c->whh16_pk[l], ctc_pack_whh16(whh.data()));
     }
     const float* ow = take((size_t)V * 2 * H);
@@ -488,6 +531,92 @@ wk_status wk_ctc_frame_argmax(wk_ctc* c, int64_t batch, int32_t T, int32_t* d_pr
     launch_ctc_pred(c->best, batch, T, c->f16 ? 1 : 0, d_pred, (hipStream_t)stream);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? WK_OK : hip_fail(e, "wk_ctc_frame_argmax launch");
+  });
+}
+
+wk_status wk_ctc_forward_train(wk_ctc* c, const float* d_feats, int64_t batch, int32_t T, float* d_log_probs,
+                               void* stream) {
+  if (!c || !d_feats || !d_log_probs || batch <= 0 || T <= 0) return invalid("wk_ctc_forward_train: bad arguments");
+  const int64_t rows = batch <= INT32_MAX ? batch * (int64_t)T : INT64_MAX;
+  if (rows > INT32_MAX) return invalid("wk_ctc_forward_train: batch x frames exceeds 2^31 rows");
+  if (c->f16) return fail(WK_ERR_UNSUPPORTED, "wk_ctc_forward_train: fp32 handles only (precision 0)");
+  return on_device(c->cfg.device, [&]() -> wk_status {
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e;
+    if ((size_t)rows > c->tn_rows) {   // grows on first use of a larger batch x T, as the inference workspace does
+      if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(e, "sync");
+      if ((e = alloc_tn(c, (size_t)rows)) != hipSuccess)
+        return e == hipErrorOutOfMemory ? WK_ERR_NO_MEMORY : hip_fail(e, "wk_ctc_forward_train workspace");
+    }
+    c->tn_batch = 0;   // (set once every stage is enqueued)
+    const int H = kH, V = c->cfg.vocab;
+    if ((e = hipMemcpyAsync(c->tn_feats, d_feats, sizeof(float) * rows * kMels, hipMemcpyDeviceToDevice, st)) != hipSuccess)
+      return hip_fail(e, "hipMemcpyAsync");
+    // wk_ctc_forward's fp32 stages, kernel for kernel, on the training buffers
+    launch_ctc_encoder(false, d_feats, (int)batch, T, c->enc_w, c->enc_b, c->ln_g, c->ln_b, nullptr, c->tn_x0.get(), c->n_cu, st);
+    for (int l = 0; l < 2; ++l) {
+      const wk_status s = ctc_gemm_nt(st, rows, 6 * H, l == 0 ? H : 2 * H, l == 0 ? c->tn_x0.get() : c->tn_y[0].get(), c->wih[l],
+                                      c->tn_gi[l].get(), false);
+      if (s != WK_OK) return s;
+      launch_ctc_gru(false, c->tn_gi[l].get(), c->whh_pk[l].get(), c->bih[l], c->bhh[l], batch, T, c->tn_y[l].get(), st);
+    }
+    const wk_status s = ctc_gemm_nt(st, rows, V, 2 * H, c->tn_y[1].get(), c->out_w, c->tn_logits.get(), false);
+    if (s != WK_OK) return s;
+    launch_ctc_argmax(false, c->tn_logits.get(), c->out_b, rows, V, d_log_probs, nullptr, 0, 0, st);
+    e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "wk_ctc_forward_train launch");
+    c->tn_batch = batch;
+    c->tn_T = T;
+    return WK_OK;
+  });
+}
+
+wk_status wk_ctc_backward(wk_ctc* c, int64_t batch, int32_t T, const float* d_dlogits, float* d_grads, float* d_grad_norm,
+                          void* stream) {
+  if (!c || !d_dlogits || !d_grads || batch <= 0 || T <= 0) return invalid("wk_ctc_backward: bad arguments");
+  if (batch > INT32_MAX || batch * (int64_t)T > INT32_MAX) return invalid("wk_ctc_backward: batch x frames exceeds 2^31 rows");
+  if (c->f16) return fail(WK_ERR_UNSUPPORTED, "wk_ctc_backward: fp32 handles only (precision 0)");
+  if (batch != c->tn_batch || T != c->tn_T || (size_t)(batch * (int64_t)T) > c->tn_rows)
+    return invalid("wk_ctc_backward: batch and T must be those of the handle's last wk_ctc_forward_train");
+  return on_device(c->cfg.device, [&]() -> wk_status {
+    CtcBwd a{};
+    a.B = batch;
+    a.T = T;
+    a.V = c->cfg.vocab;
+    a.n_cu = c->n_cu;
+    a.feats = c->tn_feats;
+    a.x0 = c->tn_x0;
+    a.enc_w = c->enc_w;
+    a.enc_b = c->enc_b;
+    a.ln_g = c->ln_g;
+    a.out_w = c->out_w;
+    for (int l = 0; l < 2; ++l) {
+      a.gi[l] = c->tn_gi[l];
+      a.y[l] = c->tn_y[l];
+      a.wih[l] = c->wih[l];
+      a.whh[l] = c->whh[l];
+      a.whht_pk[l] = c->whht_pk[l];
+      a.bih[l] = c->bih[l];
+      a.bhh[l] = c->bhh[l];
+    }
+    a.hprev = c->tn_hprev;
+    a.dya = c->tn_dya;
+    a.dyb = c->tn_dyb;
+    a.gh = c->tn_gh;
+    a.da_i = c->tn_dai;
+    a.da_h = c->tn_dah;
+    a.coef = c->tn_coef;
+    a.pre = c->tn_pre;
+    a.t0 = c->tn_t0;
+    a.t1 = c->tn_t1;
+    a.part = c->tn_part;
+    a.part_floats = ctc_bwd_part_floats(c->cfg.vocab, (int64_t)c->tn_rows);
+    a.dlogits = d_dlogits;
+    a.grads = d_grads;
+    a.norm = d_grad_norm;
+    launch_ctc_backward(a, (hipStream_t)stream);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? WK_OK : hip_fail(e, "wk_ctc_backward launch");
   });
 }
 

@@ -6,6 +6,7 @@
 //   wk_ctc_dense.hip   X2a  encoder (fp32 / fp16), the block GEMM, fp16 <-> fp32 copy
 //   wk_ctc_gru.hip     X2b  the three recurrences and their weight packers
 //   wk_ctc_out.hip     X2c / X3  output layer + argmax kernels, re-score, greedy decode
+//   wk_ctc_bwd.hip     the fp32 backward pass: parameter gradients from the gradient at the logits
 //
 // Layout constants stay with the kernel that defines the layout: each packer
 // and each grid computation sits in the kernel's own unit, so none is needed
@@ -114,5 +115,28 @@ void launch_ctc_rescore(const __half* y, const float* w, const float* bias, int6
                         hipStream_t st);
 void launch_ctc_greedy(const int* best, int64_t B, int T, int* tokens, int* lengths, int tm, hipStream_t st);
 void launch_ctc_pred(const int* best, int64_t B, int T, int tm, int* pred, hipStream_t st);
+
+// ---- wk_ctc_bwd.hip ---------------------------------------------------------
+// W_hh [2 dir][384][128] fp32 -> ctc_gru_bptt_kernel's fragments of W_hh^T ([2][8 unit tiles][96 k-steps][64 lanes]).
+std::vector<float> ctc_pack_whht(const float* whh);
+// Floats of the split-K partials workspace (CtcBwd::part) for vocabulary V and rows = B T.
+size_t ctc_bwd_part_floats(int V, int64_t rows);
+// One backward pass (fp32), all device pointers.  Saved by the training
+// forward: feats [rows][80], x0 [rows][128], gi[l] [rows][768] (no bias), y[l]
+// [rows][256].  Weights as uploaded by wk_ctc_create (wih[l] [768][din], whh[l]
+// [2][384][128], bih / bhh [768]).  Scratch: hprev, dya, dyb [rows][256]; gh,
+// da_i, da_h [rows][768]; coef [rows][1280]; pre, t0, t1 [rows][128]; part.
+// grads: the parameter blob's layout; norm (or null): its 2-norm.
+struct CtcBwd {
+  int64_t B;
+  int T, V, n_cu;
+  const float *feats, *x0, *gi[2], *y[2];
+  const float *enc_w, *enc_b, *ln_g, *wih[2], *whh[2], *whht_pk[2], *bih[2], *bhh[2], *out_w;
+  float *hprev, *dya, *dyb, *gh, *da_i, *da_h, *coef, *pre, *t0, *t1, *part;
+  size_t part_floats;   // of part: ctc_bwd_part_floats(V, rows), or more
+  const float* dlogits;
+  float *grads, *norm;
+};
+void launch_ctc_backward(const CtcBwd& a, hipStream_t st);
 
 }  // namespace wk

@@ -35,7 +35,7 @@ EXPORTS = ("wk_create", "wk_destroy", "wk_mfcc", "wk_cnn", "wk_forward", "wk_syn
            "wk_esp_mfcc_destroy", "wk_scan", "wk_scan_workspace_bytes", "wk_trainer_create", "wk_trainer_destroy",
            "wk_trainer_grad", "wk_trainer_step", "wk_trainer_weights", "wk_quant_spec_default", "wk_set_quant",
            "wk_get_quant", "wk_quant_weights", "wk_calibrate_workspace_bytes", "wk_calibrate",
-           "wk_ctc_loss_workspace_bytes", "wk_ctc_loss")
+           "wk_ctc_loss_workspace_bytes", "wk_ctc_loss", "wk_ctc_forward_train", "wk_ctc_backward")
 WK_CTC_REDUCTION = {"none": 0, "sum": 1, "mean": 2}
 WK_NUM_INT8_WEIGHTS = 3 * 13 * 32 + 3 * 32 * 64 + 3 * 64 * 128 + 128 * 64 + 64
 WK_QUANT_TENSORS = 7
@@ -146,6 +146,11 @@ def _declare(L):
         L.wk_ctc_loss_workspace_bytes.restype = i64
         L.wk_ctc_loss.argtypes = [vp, i64, i32, i32, vp, i32, vp, vp, i32, i32, i32, C.c_float, vp, vp, vp, vp, i32, vp]
         L.wk_ctc_loss.restype = i32
+    if hasattr(L, "wk_ctc_backward"):
+        L.wk_ctc_forward_train.argtypes = [vp, vp, i64, i32, vp, vp]
+        L.wk_ctc_forward_train.restype = i32
+        L.wk_ctc_backward.argtypes = [vp, i64, i32, vp, vp, vp, vp]
+        L.wk_ctc_backward.restype = i32
     for name in ("wk_create", "wk_destroy", "wk_mfcc", "wk_cnn", "wk_forward", "wk_synth_clips", "wk_normalize",
                  "wk_stream_create", "wk_stream_destroy", "wk_stream_reset", "wk_stream_push", "wk_ctc_create",
                  "wk_ctc_destroy", "wk_ctc_features", "wk_ctc_forward", "wk_wav_read", "wk_wav_load_batch",

@@ -9,6 +9,8 @@ inference surface on the HIP path (wk_ctc_* in the C ABI).
     texts = model.transcribe_text(audio)                 # device decode, then the map
     loss = wakeword.ctc_loss(log_probs, targets, input_lengths, target_lengths)   # nn.CTCLoss(blank=0), ctc.py:369
     loss = model.loss(feats, targets, input_lengths, target_lengths)              # validation loss, ctc.py:409-425
+    loss, grads, norm = model.loss_and_grad(feats, targets, input_lengths, target_lengths)   # ctc.py:393-401, fp32
+    lp = model.forward_train(feats); flat = model.backward(dlogits); grads = unpack_grads(flat, V)   # its pieces
 
 A state dict is bound BY NAME: its keys must be exactly GRU_CTC_Model's
 (ctc_state_dict_spec(), ctc.py:119-146: audio_encoder.{0,1}, gru.*_l{k}[_reverse],
@@ -98,6 +100,22 @@ def pack_state_dict(sd: Mapping[str, object], vocab: int, hidden: int = 128, lay
             raise ValueError(f"{k}: expected shape {shape}, got {tuple(a.shape)}")
         parts.append(a.reshape(-1))
     return np.concatenate(parts)
+
+
+def unpack_grads(flat, vocab: int, hidden: int = 128, layers: int = 2, n_mels: int = 80) -> dict:
+    """{state-dict key: view of `flat`} for a flat tensor or array in the
+    weight blob's layout (CTCModel.backward's gradient, or the blob itself),
+    each view in its parameter's shape."""
+    spec = ctc_state_dict_spec(vocab, hidden, layers, n_mels)
+    need = sum(int(np.prod(shape)) for _, shape in spec)
+    if flat.ndim != 1 or flat.shape[0] != need:
+        raise ValueError(f"expected a flat vector of {need} values for vocab={vocab}, got shape {tuple(flat.shape)}")
+    out, off = {}, 0
+    for k, shape in spec:
+        n = int(np.prod(shape))
+        out[k] = flat[off:off + n].reshape(shape)
+        off += n
+    return out
 
 
 def tokens_to_text(seqs: Sequence[Sequence[int]], idx_to_char: Mapping[int, str]) -> List[str]:
@@ -351,6 +369,78 @@ class CTCModel:
         return_log_probs=True), then ctc_loss on the (B, T, V) log-probs."""
         _, _, lp = self.decode(feats, return_log_probs=True)
         return ctc_loss(lp, targets, input_lengths, target_lengths, reduction=reduction, batch_first=True)
+
+    # ---- parameter gradients (fp32 models; wk_ctc_forward_train / wk_ctc_backward) ----
+    def forward_train(self, feats):
+        """(B, T, 80) -> (B, T, V) log-probs on the device, bit for bit those
+        of decode(..., return_log_probs=True), with the activations backward()
+        needs kept in the model's training workspace.  The eval-mode function
+        (no dropout); no tokens are decoded."""
+        import torch
+        f = torch.as_tensor(feats, dtype=torch.float32).to(f"cuda:{self.device}").contiguous()
+        B, T, _ = f.shape
+        lp = torch.empty((B, T, self.vocab), dtype=torch.float32, device=f.device)
+        check(lib().wk_ctc_forward_train(self._h, C.c_void_p(f.data_ptr()), B, T, C.c_void_p(lp.data_ptr()),
+                                         self._stream(torch)), "wk_ctc_forward_train")
+        return lp
+
+    def backward(self, dlogits, return_norm: bool = False):
+        """The gradient of every parameter as one flat float32 device tensor in
+        the weight blob's order (unpack_grads names its pieces), from dlogits
+        (B, T, V): the gradient at the logits of the last forward_train, which
+        is what wk_ctc_loss writes.  An upstream gradient G on the log-probs lp
+        converts as  dlogits = G - lp.exp() * G.sum(-1, keepdim=True).
+        return_norm: also the blob's 2-norm (a 0-d device tensor)."""
+        import torch
+        g = torch.as_tensor(dlogits, dtype=torch.float32).to(f"cuda:{self.device}").contiguous()
+        if g.dim() != 3 or g.shape[2] != self.vocab:
+            raise ValueError(f"dlogits must be (B, T, {self.vocab}), got {tuple(g.shape)}")
+        B, T, _ = g.shape
+        n = lib().wk_ctc_num_weights(C.byref(self.cfg))
+        out = torch.empty((n,), dtype=torch.float32, device=g.device)
+        norm = torch.empty((1,), dtype=torch.float32, device=g.device) if return_norm else None
+        check(lib().wk_ctc_backward(self._h, B, T, C.c_void_p(g.data_ptr()), C.c_void_p(out.data_ptr()),
+                                    C.c_void_p(norm.data_ptr()) if norm is not None else None, self._stream(torch)),
+              "wk_ctc_backward")
+        return (out, norm.reshape(())) if return_norm else out
+
+    def loss_and_grad(self, feats, targets, input_lengths, target_lengths, reduction: str = "mean",
+                      zero_infinity: bool = False):
+        """The loss half of a training step (ctc.py:390-401, without the clip
+        and the optimiser): forward_train, wk_ctc_loss with its gradient
+        output, backward.  Returns (loss, {state-dict key: gradient view},
+        gradient 2-norm), all on the device; loss is per utterance for
+        reduction="none", whose gradient is that of the sum."""
+        import torch
+        if reduction not in _lib.WK_CTC_REDUCTION:
+            raise ValueError(f"reduction must be 'none', 'sum' or 'mean', got {reduction!r}")
+        lp = self.forward_train(feats)
+        B, T, V = lp.shape
+        labels = pad_targets(targets, target_lengths).to(lp.device).contiguous()
+        in_len = torch.as_tensor(input_lengths).reshape(-1).to(device=lp.device, dtype=torch.int32).contiguous()
+        lab_len = torch.as_tensor(target_lengths).reshape(-1).to(device=lp.device, dtype=torch.int32).contiguous()
+        if labels.shape[0] != B or in_len.numel() != B or lab_len.numel() != B:
+            raise ValueError(f"batch of {B}: targets {tuple(labels.shape)}, {in_len.numel()} input and {lab_len.numel()} "
+                             f"target lengths")
+        max_label_len = labels.shape[1]
+        if max_label_len > MAX_LABEL_LEN:
+            max_label_len = int(lab_len.max())
+        L = lib()
+        nbytes = L.wk_ctc_loss_workspace_bytes(B, T, max_label_len)
+        if nbytes <= 0:
+            raise _lib.WakewordError(f"wk_ctc_loss: unsupported shape (B={B}, T={T}, max label length {max_label_len})")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=lp.device)
+        nll = torch.empty(B, dtype=torch.float32, device=lp.device)
+        loss = torch.empty(1, dtype=torch.float32, device=lp.device)
+        grad = torch.empty_like(lp)
+
+        def ptr(t):
+            return C.c_void_p(t.data_ptr())
+        check(L.wk_ctc_loss(ptr(lp), B, T, V, ptr(labels), labels.shape[1], ptr(in_len), ptr(lab_len), max_label_len,
+                            _lib.WK_CTC_REDUCTION[reduction], int(zero_infinity), 1.0, ptr(ws), ptr(nll), ptr(loss),
+                            ptr(grad), self.device, self._stream(torch)), "wk_ctc_loss")
+        flat, norm = self.backward(grad, return_norm=True)
+        return (nll if reduction == "none" else loss.reshape(())), unpack_grads(flat, self.vocab), norm
 
     def decode_predictions(self, log_probs, idx_to_char: Optional[Mapping[int, str]] = None) -> List[str]:
         """THCHS30Trainer.decode_predictions (ctc.py:453-471) with this model's map."""

@@ -312,6 +312,42 @@ wk_status wk_ctc_stage_times(wk_ctc* c, double* ms_sum /* [WK_CTC_N_STAGES] */, 
  * must be that call's (else WK_ERR_INVALID_ARG); stream-ordered after it. */
 wk_status wk_ctc_frame_argmax(wk_ctc* c, int64_t batch, int32_t T, int32_t* d_pred, void* stream);
 
+/* ---- CTC head: parameter gradients (the backward half of ctc.py:380-407) -----
+ * fp32 handles only (precision 0; a precision-1 handle: WK_ERR_UNSUPPORTED
+ * before any device work).  The function differentiated is the one
+ * wk_ctc_forward computes: the eval-mode module (no dropout is applied), as
+ * CTCModel.loss uses it.  No optimiser step and no clipping are done here.
+ *
+ * wk_ctc_forward_train: d_feats [batch][T][80] -> d_log_probs [batch][T][V],
+ * bit for bit wk_ctc_forward's fp32 log-probs (the same kernels), and keeps in
+ * a handle-owned training workspace -- apart from wk_ctc_forward's, which it
+ * leaves untouched, and grown on the first call with a larger batch*T -- what
+ * the backward needs: the features, the encoder output, each GRU layer's gate
+ * inputs x W_ih^T and outputs.  No tokens are decoded.
+ *
+ * wk_ctc_backward: d_dlogits [batch][T][V], the gradient at the logits (what
+ * wk_ctc_loss writes to d_grad; frames past an input length carry 0 and are
+ * still walked, as the reference runs the GRU over the padded length) ->
+ * d_grads [wk_ctc_num_weights], the gradient of every parameter in
+ * wk_ctc_create's blob order (a state dict and its gradient share one
+ * layout), and d_grad_norm_or_null [1], the 2-norm of that blob accumulated
+ * in double (what clip_grad_norm_ needs, ctc.py:401).  batch and T must be
+ * those of the handle's last wk_ctc_forward_train (else WK_ERR_INVALID_ARG).
+ * A caller whose upstream gradient G is on the log-probs lp converts it first:
+ * dlogits = G - exp(lp) * sum_v G.
+ *
+ * Both are stream-ordered and do not synchronise with the host (but for the
+ * workspace growth).  No floating-point atomics are used and every sum has a
+ * fixed order: the same handle and inputs give the same bits.  The saved
+ * activations belong to the handle: one stream per handle, and nothing else
+ * between a forward_train and its backward may call forward_train on it.
+ * Null pointers, batch or T <= 0, batch*T > 2^31 - 1: WK_ERR_INVALID_ARG before
+ * any launch.  The workspace takes about 4 (7000 + V) bytes per row of batch*T. */
+wk_status wk_ctc_forward_train(wk_ctc* c, const float* d_feats, int64_t batch, int32_t T, float* d_log_probs,
+                               void* stream);
+wk_status wk_ctc_backward(wk_ctc* c, int64_t batch, int32_t T, const float* d_dlogits, float* d_grads,
+                          float* d_grad_norm_or_null, void* stream);
+
 /* ---- CTC loss and its gradient (nn.CTCLoss(blank=0); ctc.py:369, :380-425) ---
  * d_log_probs [batch][T][vocab] fp32 (the layout wk_ctc_forward writes),
  * d_labels [batch][label_stride] int32, d_input_lengths / d_label_lengths
