@@ -11,14 +11,18 @@
 // layout by its unit's packer), the workspaces, stage timing, and the stage
 // sequence of wk_ctc_features / wk_ctc_forward / wk_ctc_transcribe, which
 // call the launchers declared in wk_ctc_dev.h; and, for training, the fp32
-// forward that keeps its activations (wk_ctc_forward_train) and the entry to
-// the backward pass of wk_ctc_bwd.hip (wk_ctc_backward).
+// forward that keeps its activations (wk_ctc_forward_train), the entry to
+// the backward pass of wk_ctc_bwd.hip (wk_ctc_backward), and the optimiser's
+// entry points over wk_ctc_optim.hip (wk_ctc_adam_step, wk_ctc_weights,
+// wk_ctc_set_weights, wk_ctc_optim_state, wk_ctc_set_optim_state).
 #include <stdlib.h>
 #include <string.h>
 
 #include <array>
+#include <cmath>
 #include <memory>
 #include <new>
+#include <string>
 #include <type_traits>
 
 #include "wk_ctc_dev.h"
@@ -75,6 +79,11 @@ struct wk_ctc {
   DevBuf<float> tn_hprev, tn_dya, tn_dyb, tn_gh, tn_dai, tn_dah, tn_coef, tn_pre, tn_t0, tn_t1, tn_part;
   int64_t tn_batch;     // geometry of the last wk_ctc_forward_train (wk_ctc_backward)
   int32_t tn_T;
+  // optimiser (fp32 handles; wk_ctc_adam_step): Adam's moments in blob order and the norm computed when the caller
+  // passes none, allocated and zeroed on first use; the step count is host state
+  DevBuf<float> opt_m, opt_v, opt_norm;
+  bool opt_ready;
+  int64_t opt_step;
   // stage timing (wk_ctc_profile): events recorded around each stage on the
   // call's stream, folded into per-stage sums when read or when the ring fills
   int prof;
@@ -617,6 +626,162 @@ wk_status wk_ctc_backward(wk_ctc* c, int64_t batch, int32_t T, const float* d_dl
     launch_ctc_backward(a, (hipStream_t)stream);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? WK_OK : hip_fail(e, "wk_ctc_backward launch");
+  });
+}
+
+namespace {
+
+// The handle's weight buffers in blob order (wk_ctc_create's `take` sequence).
+CtcSegTable seg_table(const wk_ctc* c) {
+  const int64_t H = kH, V = c->cfg.vocab;
+  CtcSegTable t;
+  int k = 0;
+  int64_t off = 0;
+  auto add = [&](float* p, int64_t len) {
+    t.s[k++] = {off, len, p};
+    off += len;
+  };
+  add(c->enc_w, H * kMels);
+  add(c->enc_b, H);
+  add(c->ln_g, H);
+  add(c->ln_b, H);
+  for (int l = 0; l < 2; ++l)
+    for (int d = 0; d < 2; ++d) {
+      const int64_t din = l == 0 ? H : 2 * H;
+      add(c->wih[l] + d * 3 * H * din, 3 * H * din);
+      add(c->whh[l] + d * 3 * H * H, 3 * H * H);
+      add(c->bih[l] + d * 3 * H, 3 * H);
+      add(c->bhh[l] + d * 3 * H, 3 * H);
+    }
+  add(c->out_w, V * 2 * H);
+  add(c->out_b, V);
+  return t;
+}
+
+// Every W_hh layout an fp32 entry point reads, from whh[l].
+void refresh_whh(const wk_ctc* c, hipStream_t st) {
+  launch_ctc_refresh({{c->whh[0], c->whh[1]}, {c->whh_pk[0], c->whh_pk[1]}, {c->whht_pk[0], c->whht_pk[1]}}, st);
+}
+
+// The weight-changing calls: fp32 handles, and not the attribution mode (its fp16 out_w16 would go stale).
+wk_status mutable_handle(const wk_ctc* c, const char* fn) {
+  if (c->f16) return fail(WK_ERR_UNSUPPORTED, (std::string(fn) + ": fp32 handles only (precision 0)").c_str());
+  if (c->mix) return fail(WK_ERR_UNSUPPORTED, (std::string(fn) + ": not on a handle created under WAKEWORD_CTC_MIX").c_str());
+  return WK_OK;
+}
+
+// Adam's state, zeroed, on first use (stream-ordered; the allocation is what may block).
+wk_status ensure_optim(wk_ctc* c, hipStream_t st, const char* fn) {
+  if (c->opt_ready) return WK_OK;
+  const size_t n = (size_t)wk_ctc_num_weights(&c->cfg);
+  hipError_t e = c->opt_m.alloc(n);
+  if (e == hipSuccess) e = c->opt_v.alloc(n);
+  if (e == hipSuccess) e = c->opt_norm.alloc(1);
+  if (e == hipSuccess) e = hipMemsetAsync(c->opt_m, 0, sizeof(float) * n, st);
+  if (e == hipSuccess) e = hipMemsetAsync(c->opt_v, 0, sizeof(float) * n, st);
+  if (e != hipSuccess) {
+    c->opt_m.reset();
+    c->opt_v.reset();
+    c->opt_norm.reset();
+    return e == hipErrorOutOfMemory ? fail(WK_ERR_NO_MEMORY, fn) : hip_fail(e, fn);
+  }
+  c->opt_step = 0;
+  c->opt_ready = true;
+  return WK_OK;
+}
+
+}  // namespace
+
+wk_status wk_ctc_weights(wk_ctc* c, float* d_out, void* stream) {
+  if (!c || !d_out) return invalid("wk_ctc_weights: null argument");
+  if (const wk_status s = mutable_handle(c, "wk_ctc_weights")) return s;
+  return on_device(c->cfg.device, [&]() -> wk_status {
+    launch_ctc_gather(seg_table(c), d_out, c->n_cu, (hipStream_t)stream);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? WK_OK : hip_fail(e, "wk_ctc_weights launch");
+  });
+}
+
+wk_status wk_ctc_set_weights(wk_ctc* c, const float* d_blob, void* stream) {
+  if (!c || !d_blob) return invalid("wk_ctc_set_weights: null argument");
+  if (const wk_status s = mutable_handle(c, "wk_ctc_set_weights")) return s;
+  return on_device(c->cfg.device, [&]() -> wk_status {
+    launch_ctc_scatter(seg_table(c), d_blob, c->n_cu, (hipStream_t)stream);
+    refresh_whh(c, (hipStream_t)stream);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? WK_OK : hip_fail(e, "wk_ctc_set_weights launch");
+  });
+}
+
+wk_status wk_ctc_adam_step(wk_ctc* c, const wk_ctc_adam* opt, const float* d_grads, const float* d_norm_or_null,
+                           void* stream) {
+  if (!c || !opt || !d_grads) return invalid("wk_ctc_adam_step: null argument");
+  if (!std::isfinite(opt->lr) || opt->lr < 0.0f) return invalid("wk_ctc_adam_step: lr must be finite and >= 0");
+  if (!(opt->beta1 >= 0.0f && opt->beta1 < 1.0f) || !(opt->beta2 >= 0.0f && opt->beta2 < 1.0f))
+    return invalid("wk_ctc_adam_step: beta1 and beta2 must lie in [0, 1)");
+  if (!(opt->eps > 0.0f)) return invalid("wk_ctc_adam_step: eps must be > 0");
+  if (!(opt->weight_decay >= 0.0f)) return invalid("wk_ctc_adam_step: weight_decay must be >= 0");
+  if (std::isnan(opt->max_norm)) return invalid("wk_ctc_adam_step: max_norm is NaN (<= 0 turns the clip off)");
+  if (const wk_status s = mutable_handle(c, "wk_ctc_adam_step")) return s;
+  return on_device(c->cfg.device, [&]() -> wk_status {
+    hipStream_t st = (hipStream_t)stream;
+    if (const wk_status s = ensure_optim(c, st, "wk_ctc_adam_step: optimiser state")) return s;
+    const bool clip = opt->max_norm > 0.0f;
+    const float* norm = clip ? d_norm_or_null : nullptr;
+    if (clip && !norm) {
+      launch_ctc_bwd_norm(d_grads, wk_ctc_num_weights(&c->cfg), c->opt_norm, st);
+      norm = c->opt_norm;
+    }
+    const int64_t step = c->opt_step + 1;
+    const double b1 = opt->beta1, b2 = opt->beta2;
+    const double bc1 = 1.0 - pow(b1, (double)step), bc2 = 1.0 - pow(b2, (double)step);
+    const CtcAdamArgs a{opt->max_norm, opt->weight_decay,           opt->beta1,        (float)(1.0 - b1), opt->beta2,
+                        (float)(1.0 - b2), (float)((double)opt->lr / bc1), (float)sqrt(bc2), opt->eps};
+    launch_ctc_adam(seg_table(c), d_grads, c->opt_m, c->opt_v, norm, a, c->n_cu, st);
+    refresh_whh(c, st);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "wk_ctc_adam_step launch");
+    c->opt_step = step;
+    return WK_OK;
+  });
+}
+
+wk_status wk_ctc_optim_state(wk_ctc* c, float* d_m, float* d_v, int64_t* step, void* stream) {
+  if (!c) return invalid("wk_ctc_optim_state: null handle");
+  if (const wk_status s = mutable_handle(c, "wk_ctc_optim_state")) return s;
+  return on_device(c->cfg.device, [&]() -> wk_status {
+    hipStream_t st = (hipStream_t)stream;
+    const size_t bytes = sizeof(float) * (size_t)wk_ctc_num_weights(&c->cfg);
+    hipError_t e = hipSuccess;
+    float* const out[2] = {d_m, d_v};
+    const float* const src[2] = {c->opt_m, c->opt_v};
+    for (int i = 0; i < 2 && e == hipSuccess; ++i) {   // (a handle that never stepped: zeros, step 0)
+      if (!out[i]) continue;
+      e = c->opt_ready ? hipMemcpyAsync(out[i], src[i], bytes, hipMemcpyDeviceToDevice, st) : hipMemsetAsync(out[i], 0, bytes, st);
+    }
+    if (e != hipSuccess) return hip_fail(e, "wk_ctc_optim_state");
+    if (step) *step = c->opt_ready ? c->opt_step : 0;
+    return WK_OK;
+  });
+}
+
+wk_status wk_ctc_set_optim_state(wk_ctc* c, const float* d_m_or_null, const float* d_v_or_null, int64_t step, void* stream) {
+  if (!c) return invalid("wk_ctc_set_optim_state: null handle");
+  if (step < 0) return invalid("wk_ctc_set_optim_state: negative step");
+  if (const wk_status s = mutable_handle(c, "wk_ctc_set_optim_state")) return s;
+  return on_device(c->cfg.device, [&]() -> wk_status {
+    hipStream_t st = (hipStream_t)stream;
+    if (const wk_status s = ensure_optim(c, st, "wk_ctc_set_optim_state: optimiser state")) return s;
+    const size_t bytes = sizeof(float) * (size_t)wk_ctc_num_weights(&c->cfg);
+    float* const dst[2] = {c->opt_m, c->opt_v};
+    const float* const src[2] = {d_m_or_null, d_v_or_null};
+    for (int i = 0; i < 2; ++i) {
+      const hipError_t e = src[i] ? hipMemcpyAsync(dst[i], src[i], bytes, hipMemcpyDeviceToDevice, st)
+                                  : hipMemsetAsync(dst[i], 0, bytes, st);
+      if (e != hipSuccess) return hip_fail(e, "wk_ctc_set_optim_state");
+    }
+    c->opt_step = step;
+    return WK_OK;
   });
 }
 

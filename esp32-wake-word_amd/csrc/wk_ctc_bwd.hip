@@ -513,4 +513,8 @@ void launch_ctc_backward(const CtcBwd& a, hipStream_t st) {
   if (a.norm) hipLaunchKernelGGL(ctc_bwd_norm_kernel, dim3(1), dim3(1024), 0, st, g, (int64_t)(o_outb + V), a.norm);
 }
 
+void launch_ctc_bwd_norm(const float* g, int64_t n, float* out, hipStream_t st) {
+  hipLaunchKernelGGL(ctc_bwd_norm_kernel, dim3(1), dim3(1024), 0, st, g, n, out);
+}
+
 }  // namespace wk

@@ -7,6 +7,7 @@
 //   wk_ctc_gru.hip     X2b  the three recurrences and their weight packers
 //   wk_ctc_out.hip     X2c / X3  output layer + argmax kernels, re-score, greedy decode
 //   wk_ctc_bwd.hip     the fp32 backward pass: parameter gradients from the gradient at the logits
+//   wk_ctc_optim.hip   clip + Adam on the handle's weights, the W_hh fragments again, blob <-> buffers
 //
 // Layout constants stay with the kernel that defines the layout: each packer
 // and each grid computation sits in the kernel's own unit, so none is needed
@@ -138,5 +139,39 @@ struct CtcBwd {
   float *grads, *norm;
 };
 void launch_ctc_backward(const CtcBwd& a, hipStream_t st);
+// out[0] = the 2-norm of g [n], accumulated in double in a fixed order (ctc_bwd_norm_kernel, as launch_ctc_backward runs it).
+void launch_ctc_bwd_norm(const float* g, int64_t n, float* out, hipStream_t st);
+
+// ---- wk_ctc_optim.hip -------------------------------------------------------
+// The weight blob as the handle keeps it: segment k is blob[off, off + len) and
+// lives at p (22 segments: 4 encoder, 2 layers x 2 directions x {W_ih, W_hh,
+// b_ih, b_hh}, 2 output).  Every off and every len but the last (out_b [V]) is
+// a multiple of 4 floats, and every p is 16-byte aligned.  Passed by value.
+constexpr int kCtcSegs = 22;
+struct CtcSeg {
+  int64_t off, len;
+  float* p;
+};
+struct CtcSegTable {
+  CtcSeg s[kCtcSegs];
+};
+// Adam's constants for one step, rounded to fp32 from double on the host:
+// step_size = lr / (1 - beta1^t), sqrt_bc2 = sqrt(1 - beta2^t).
+struct CtcAdamArgs {
+  float max_norm, weight_decay, beta1, one_minus_beta1, beta2, one_minus_beta2, step_size, sqrt_bc2, eps;
+};
+// Clip + Adam in place on the table's buffers; g, m, v [blob].  norm != null:
+// the gradient is first scaled by min(1, max_norm / (norm[0] + 1e-6)), read on the device.
+void launch_ctc_adam(const CtcSegTable& tab, const float* g, float* m, float* v, const float* norm, const CtcAdamArgs& a,
+                     int n_cu, hipStream_t st);
+// whh_pk[l] and whht_pk[l] from whh[l] [2 dir][384][128]: what ctc_pack_whh and ctc_pack_whht give, bit for bit.
+struct CtcWhhSet {
+  const float* whh[2];
+  float *whh_pk[2], *whht_pk[2];
+};
+void launch_ctc_refresh(const CtcWhhSet& w, hipStream_t st);
+// The table's buffers -> blob, and blob -> the table's buffers.
+void launch_ctc_gather(const CtcSegTable& tab, float* blob, int n_cu, hipStream_t st);
+void launch_ctc_scatter(const CtcSegTable& tab, const float* blob, int n_cu, hipStream_t st);
 
 }  // namespace wk

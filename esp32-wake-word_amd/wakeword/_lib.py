@@ -35,7 +35,8 @@ EXPORTS = ("wk_create", "wk_destroy", "wk_mfcc", "wk_cnn", "wk_forward", "wk_syn
            "wk_esp_mfcc_destroy", "wk_scan", "wk_scan_workspace_bytes", "wk_trainer_create", "wk_trainer_destroy",
            "wk_trainer_grad", "wk_trainer_step", "wk_trainer_weights", "wk_quant_spec_default", "wk_set_quant",
            "wk_get_quant", "wk_quant_weights", "wk_calibrate_workspace_bytes", "wk_calibrate",
-           "wk_ctc_loss_workspace_bytes", "wk_ctc_loss", "wk_ctc_forward_train", "wk_ctc_backward")
+           "wk_ctc_loss_workspace_bytes", "wk_ctc_loss", "wk_ctc_forward_train", "wk_ctc_backward", "wk_ctc_weights",
+           "wk_ctc_set_weights", "wk_ctc_adam_step", "wk_ctc_optim_state", "wk_ctc_set_optim_state")
 WK_CTC_REDUCTION = {"none": 0, "sum": 1, "mean": 2}
 WK_NUM_INT8_WEIGHTS = 3 * 13 * 32 + 3 * 32 * 64 + 3 * 64 * 128 + 128 * 64 + 64
 WK_QUANT_TENSORS = 7
@@ -56,6 +57,11 @@ class WkCtcConfig(C.Structure):
 class WkAdamW(C.Structure):
     _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
                 ("weight_decay", C.c_float)]
+
+
+class WkCtcAdam(C.Structure):
+    _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
+                ("weight_decay", C.c_float), ("max_norm", C.c_float)]
 
 
 class WkQuantSpec(C.Structure):
@@ -151,6 +157,15 @@ def _declare(L):
         L.wk_ctc_forward_train.restype = i32
         L.wk_ctc_backward.argtypes = [vp, i64, i32, vp, vp, vp, vp]
         L.wk_ctc_backward.restype = i32
+    if hasattr(L, "wk_ctc_adam_step"):
+        L.wk_ctc_weights.argtypes = [vp, vp, vp]
+        L.wk_ctc_set_weights.argtypes = [vp, vp, vp]
+        L.wk_ctc_adam_step.argtypes = [vp, C.POINTER(WkCtcAdam), vp, vp, vp]
+        L.wk_ctc_optim_state.argtypes = [vp, vp, vp, C.POINTER(i64), vp]
+        L.wk_ctc_set_optim_state.argtypes = [vp, vp, vp, i64, vp]
+        for name in ("wk_ctc_weights", "wk_ctc_set_weights", "wk_ctc_adam_step", "wk_ctc_optim_state",
+                     "wk_ctc_set_optim_state"):
+            getattr(L, name).restype = i32
     for name in ("wk_create", "wk_destroy", "wk_mfcc", "wk_cnn", "wk_forward", "wk_synth_clips", "wk_normalize",
                  "wk_stream_create", "wk_stream_destroy", "wk_stream_reset", "wk_stream_push", "wk_ctc_create",
                  "wk_ctc_destroy", "wk_ctc_features", "wk_ctc_forward", "wk_wav_read", "wk_wav_load_batch",

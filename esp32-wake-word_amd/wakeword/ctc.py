@@ -11,6 +11,8 @@ inference surface on the HIP path (wk_ctc_* in the C ABI).
     loss = model.loss(feats, targets, input_lengths, target_lengths)              # validation loss, ctc.py:409-425
     loss, grads, norm = model.loss_and_grad(feats, targets, input_lengths, target_lengths)   # ctc.py:393-401, fp32
     lp = model.forward_train(feats); flat = model.backward(dlogits); grads = unpack_grads(flat, V)   # its pieces
+    model.adam_step(grads, norm)                         # clip_grad_norm_(5.0) + Adam(lr=1e-3) in place, ctc.py:401-402
+    flat = model.weights(); model.set_weights(blob_or_state_dict)   # the weights after creation (wakeword.CTCTrainer: the loop)
 
 A state dict is bound BY NAME: its keys must be exactly GRU_CTC_Model's
 (ctc_state_dict_spec(), ctc.py:119-146: audio_encoder.{0,1}, gru.*_l{k}[_reverse],
@@ -411,6 +413,12 @@ class CTCModel:
         output, backward.  Returns (loss, {state-dict key: gradient view},
         gradient 2-norm), all on the device; loss is per utterance for
         reduction="none", whose gradient is that of the sum."""
+        loss, flat, norm = self._loss_and_flat_grad(feats, targets, input_lengths, target_lengths, reduction, zero_infinity)
+        return loss, unpack_grads(flat, self.vocab), norm
+
+    def _loss_and_flat_grad(self, feats, targets, input_lengths, target_lengths, reduction: str = "mean",
+                            zero_infinity: bool = False):
+        """loss_and_grad with the gradient as backward() returns it: one flat tensor."""
         import torch
         if reduction not in _lib.WK_CTC_REDUCTION:
             raise ValueError(f"reduction must be 'none', 'sum' or 'mean', got {reduction!r}")
@@ -440,7 +448,84 @@ class CTCModel:
                             _lib.WK_CTC_REDUCTION[reduction], int(zero_infinity), 1.0, ptr(ws), ptr(nll), ptr(loss),
                             ptr(grad), self.device, self._stream(torch)), "wk_ctc_loss")
         flat, norm = self.backward(grad, return_norm=True)
-        return (nll if reduction == "none" else loss.reshape(())), unpack_grads(flat, self.vocab), norm
+        return (nll if reduction == "none" else loss.reshape(())), flat, norm
+
+    # ---- the weights after creation, and the optimiser (fp32 models; wk_ctc_adam_step and its companions) ----
+    def num_weights(self) -> int:
+        return int(lib().wk_ctc_num_weights(C.byref(self.cfg)))
+
+    def _flat(self, t, what: str):
+        """`t` as a flat float32 device tensor of num_weights() values."""
+        import torch
+        f = torch.as_tensor(t, dtype=torch.float32).to(f"cuda:{self.device}").reshape(-1).contiguous()
+        if f.numel() != self.num_weights():
+            raise ValueError(f"{what}: expected {self.num_weights()} values for vocab={self.vocab}, got {f.numel()}")
+        return f
+
+    def weights(self):
+        """The current weights as one flat float32 device tensor in the blob's
+        order (unpack_grads names its pieces); stream-ordered, no host sync."""
+        import torch
+        out = torch.empty((self.num_weights(),), dtype=torch.float32, device=f"cuda:{self.device}")
+        check(lib().wk_ctc_weights(self._h, C.c_void_p(out.data_ptr()), self._stream(torch)), "wk_ctc_weights")
+        return out
+
+    def state_dict(self) -> Dict[str, np.ndarray]:
+        """{GRU_CTC_Model state-dict key: numpy array} of the current weights."""
+        return {k: v.copy() for k, v in unpack_grads(self.weights().cpu().numpy(), self.vocab).items()}
+
+    def set_weights(self, weights) -> None:
+        """Replace the weights in place: a flat blob (host or device), a state
+        dict or an nn.Module.  Every layout the kernels read is rebuilt on the
+        device; the optimiser state is left as it is."""
+        import torch
+        if hasattr(weights, "state_dict") and callable(weights.state_dict):
+            weights = weights.state_dict()
+        if isinstance(weights, Mapping):
+            weights = pack_state_dict(weights, self.vocab)
+        w = self._flat(weights, "set_weights")
+        check(lib().wk_ctc_set_weights(self._h, C.c_void_p(w.data_ptr()), self._stream(torch)), "wk_ctc_set_weights")
+
+    def adam_step(self, grads, norm=None, lr: float = 1e-3, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
+                  weight_decay: float = 0.0, max_norm: float = 5.0) -> None:
+        """clip_grad_norm_(max_norm) then one torch.optim.Adam step (ctc.py:368,
+        :401-402) on the model's own weights, in place.  grads: the flat
+        gradient (backward's output) or a {key: gradient} dict; norm: its
+        2-norm as a device tensor (loss_and_grad's), computed on the device
+        when None.  max_norm <= 0: no clip.  No host sync."""
+        import torch
+        if isinstance(grads, Mapping):
+            grads = torch.cat([torch.as_tensor(grads[k]).reshape(-1) for k, _ in ctc_state_dict_spec(self.vocab)])
+        g = self._flat(grads, "adam_step")
+        n = None
+        if norm is not None:
+            n = torch.as_tensor(norm, dtype=torch.float32).to(g.device).reshape(-1).contiguous()
+            if n.numel() != 1:
+                raise ValueError(f"norm must hold one value, got {n.numel()}")
+        opt = _lib.WkCtcAdam(lr, betas[0], betas[1], eps, weight_decay, max_norm)
+        check(lib().wk_ctc_adam_step(self._h, C.byref(opt), C.c_void_p(g.data_ptr()),
+                                     C.c_void_p(n.data_ptr()) if n is not None else None, self._stream(torch)),
+              "wk_ctc_adam_step")
+
+    def optim_state(self):
+        """(m, v, step): Adam's moments as flat device tensors (zeros before
+        the first step) and the number of steps taken."""
+        import torch
+        m = torch.empty((self.num_weights(),), dtype=torch.float32, device=f"cuda:{self.device}")
+        v = torch.empty_like(m)
+        step = C.c_int64(0)
+        check(lib().wk_ctc_optim_state(self._h, C.c_void_p(m.data_ptr()), C.c_void_p(v.data_ptr()), C.byref(step),
+                                       self._stream(torch)), "wk_ctc_optim_state")
+        return m, v, int(step.value)
+
+    def set_optim_state(self, m=None, v=None, step: int = 0) -> None:
+        """Adam's moments and step count; None means zeros, so the defaults reset the optimiser."""
+        import torch
+        mm = self._flat(m, "set_optim_state m") if m is not None else None
+        vv = self._flat(v, "set_optim_state v") if v is not None else None
+        check(lib().wk_ctc_set_optim_state(self._h, C.c_void_p(mm.data_ptr()) if mm is not None else None,
+                                           C.c_void_p(vv.data_ptr()) if vv is not None else None, int(step),
+                                           self._stream(torch)), "wk_ctc_set_optim_state")
 
     def decode_predictions(self, log_probs, idx_to_char: Optional[Mapping[int, str]] = None) -> List[str]:
         """THCHS30Trainer.decode_predictions (ctc.py:453-471) with this model's map."""

@@ -348,6 +348,54 @@ wk_status wk_ctc_forward_train(wk_ctc* c, const float* d_feats, int64_t batch, i
 wk_status wk_ctc_backward(wk_ctc* c, int64_t batch, int32_t T, const float* d_dlogits, float* d_grads,
                           float* d_grad_norm_or_null, void* stream);
 
+/* ---- CTC head: the optimiser (clip_grad_norm_ + optim.Adam; ctc.py:368, :401-402) ----
+ * fp32 handles only (a precision-1 handle, and a handle created under
+ * WAKEWORD_CTC_MIX, whose fp16 output weights would go stale:
+ * WK_ERR_UNSUPPORTED from all five calls).  A handle keeps its weights as
+ * per-tensor device buffers, some of them derived layouts of W_hh; these calls
+ * change them in place, and when one returns every buffer an fp32 entry point
+ * reads holds, stream-ordered, exactly what wk_ctc_create would have uploaded
+ * for the current blob: wk_ctc_forward, wk_ctc_forward_train and
+ * wk_ctc_backward all see the new weights.
+ *
+ * wk_ctc_adam_step, with g = d_grads [wk_ctc_num_weights] (wk_ctc_backward's
+ * layout) and t = the handle's step count + 1, per element and in fp32:
+ *   coef = max_norm > 0 ? min(1, max_norm / (norm + 1e-6)) : 1
+ *   g = coef g + weight_decay p;  m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) g g
+ *   p -= lr / (1 - beta1^t) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
+ * (torch.optim.Adam without amsgrad, L2 weight decay; the bias corrections are
+ * computed on the host in double).  norm is read on the device from
+ * d_norm_or_null [1] (what wk_ctc_backward wrote), or, when that is NULL and
+ * max_norm > 0, computed from d_grads by wk_ctc_backward's own norm kernel into
+ * a handle-owned float: the same bits either way.  A non-finite norm propagates
+ * as in clip_grad_norm_(error_if_nonfinite=False): inf gives coef 0 (and NaN
+ * where a gradient is inf), NaN makes every weight NaN.  The moments and the
+ * step count live in the handle, allocated and zeroed by the first
+ * wk_ctc_adam_step or wk_ctc_set_optim_state (the only time a call may block
+ * the host); nothing is allocated afterwards.  A step is a fixed number of
+ * launches (Adam, the W_hh layouts, and the norm when it is not passed),
+ * whatever V and the batch.  No atomics: every element is written by one
+ * thread, so equal inputs give equal bits.  The step count is host state: a
+ * captured graph must not contain wk_ctc_adam_step.  One stream per handle.
+ *
+ * wk_ctc_weights gathers the current weights into d_out [wk_ctc_num_weights]
+ * (blob order); wk_ctc_set_weights scatters d_blob into the handle and rebuilds
+ * the derived layouts (the optimiser state is left as it is).
+ * wk_ctc_optim_state copies m and v (either may be NULL) and the step count out
+ * (zeros and 0 before the first step); wk_ctc_set_optim_state copies them in,
+ * NULL meaning zeros: (NULL, NULL, 0) resets the optimiser.
+ * WK_ERR_INVALID_ARG before any device work: a null handle, opt, d_grads,
+ * d_out or d_blob; lr negative or not finite; a beta outside [0, 1); eps <= 0;
+ * weight_decay < 0; a NaN; a negative step. */
+typedef struct { float lr, beta1, beta2, eps, weight_decay, max_norm; } wk_ctc_adam;   /* ctc.py:368,401: 1e-3, .9, .999, 1e-8, 0, 5 */
+wk_status wk_ctc_weights(wk_ctc* c, float* d_out /* [wk_ctc_num_weights] */, void* stream);
+wk_status wk_ctc_set_weights(wk_ctc* c, const float* d_blob, void* stream);
+wk_status wk_ctc_adam_step(wk_ctc* c, const wk_ctc_adam* opt, const float* d_grads, const float* d_norm_or_null,
+                           void* stream);
+wk_status wk_ctc_optim_state(wk_ctc* c, float* d_m, float* d_v, int64_t* step, void* stream);
+wk_status wk_ctc_set_optim_state(wk_ctc* c, const float* d_m_or_null, const float* d_v_or_null, int64_t step,
+                                 void* stream);
+
 /* ---- CTC loss and its gradient (nn.CTCLoss(blank=0); ctc.py:369, :380-425) ---
  * d_log_probs [batch][T][vocab] fp32 (the layout wk_ctc_forward writes),
  * d_labels [batch][label_stride] int32, d_input_lengths / d_label_lengths
