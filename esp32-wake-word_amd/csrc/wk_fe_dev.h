@@ -584,7 +584,23 @@ __device__ __forceinline__ void mel_dispatch(int wave, const float* p, float* l)
 
 // CMVN over the 63 lanes of one coefficient row (extract_mfcc.py:76-80):
 // mean, unbiased std, std==0 -> 1, (x - mean) / (std + 1e-8).
+//
+// A row of equal values (digital silence: every frame has the same bits) has
+// std == 0 and normalises to 0.0 in the reference.  In fp32 the sum of 63 equal
+// values divided by 63 need not round to the value: then x - mean was an ulp in
+// every lane and the whole row came out +-sqrt(62/63).  Such a row is therefore
+// taken as a row of zeros, whose statistics are exact; a row with any two
+// values different is untouched.  dct_cmvn_clip (wk_fused_cnn_role.h) and
+// wk_normalize_kernel (wk_misc.hip) follow the same rule.
+// (The ballot is a statement of its own, outside any select: every lane takes part.)
+__device__ __forceinline__ bool cmvn_row_is_flat(float v, bool valid) {
+  const float p = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__float_as_int(v), 0));   // frame 0: always valid
+  return __builtin_amdgcn_ballot_w64(valid & (v != p)) == 0;
+}
+
 __device__ __forceinline__ float cmvn_lane(float v, bool valid, int n) {
+  const bool flat = cmvn_row_is_flat(v, valid);
+  v = flat ? 0.0f : v;
   const float mean = wave_sum(valid ? v : 0.0f) / (float)n;
   const float d = valid ? v - mean : 0.0f;
   float sd = sqrtf(wave_sum(d * d) / (float)(n - 1));
@@ -594,6 +610,9 @@ __device__ __forceinline__ float cmvn_lane(float v, bool valid, int n) {
 
 // Two independent coefficient rows at once (interleaved reductions).
 __device__ __forceinline__ void cmvn_lane2(float& v0, float& v1, bool valid, int n) {
+  const bool flat0 = cmvn_row_is_flat(v0, valid), flat1 = cmvn_row_is_flat(v1, valid);
+  v0 = flat0 ? 0.0f : v0;
+  v1 = flat1 ? 0.0f : v1;
   const float m0 = wave_sum(valid ? v0 : 0.0f) / (float)n;
   const float m1 = wave_sum(valid ? v1 : 0.0f) / (float)n;
   const float d0 = valid ? v0 - m0 : 0.0f;

@@ -65,6 +65,23 @@ __device__ __forceinline__ void dct_cmvn_clip(const float* __restrict__ lbuf, in
     for (int nt = 0; nt < 4; ++nt) d[nt] = mfma4(dA[s], b[nt], d[nt]);
   }
   const bool v3 = li != 15;   // tile 3 column 15 = frame 63 (padding)
+  // cmvn_lane's rule (wk_fe_dev.h): a coefficient whose 63 frames are equal
+  // (digital silence) is taken as a row of zeros and normalises to exactly 0.0;
+  // sum * (1/63) of 63 equal values need not round to the value.  A row is flat
+  // when each lane's frames are equal and frame 4 li equals frame 4 (li + 1):
+  // row_shl:1 brings the next lane's value, lane 15 keeps its own.  The
+  // select sits before all arithmetic, which rows with two different values
+  // go through unchanged.
+  const int row0 = lane & 48;   // the first lane of this lane's 16-lane row
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const float a = d[0][r];
+    const float nx = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(a), __float_as_int(a), 0x101, 0xF, 0xF, false));
+    const bool ne = (a != d[1][r]) | (a != d[2][r]) | (v3 & (a != d[3][r])) | (a != nx);
+    const bool flat = ((__builtin_amdgcn_ballot_w64(ne) >> row0) & 0xFFFFull) == 0;
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) d[nt][r] = flat ? 0.0f : d[nt][r];
+  }
   float mean[4], inv[4];
   // Reciprocal constants, v_sqrt_f32 and v_rcp_f32 (each <= 1 ulp) instead of
   // IEEE divisions and the libm square root: 12 divisions per clip had

@@ -51,17 +51,24 @@ __global__ void wk_normalize_kernel(const float* __restrict__ in, float* __restr
   const float* x = in + row * n;
   float* y = out + row * n;
   if (method == 0 || method == 2) {  // standardization / cmvn (identical in the reference)
+    // cmvn_lane's rule (wk_fe_dev.h): a row of equal values is taken as a row
+    // of zeros, so that it normalises to exactly 0 (n >= 2: wk_normalize refuses less).
+    const float p = x[0];
+    bool ne = false;
+    for (int i = lane; i < n; i += 64) ne |= x[i] != p;
+    const bool flat = __builtin_amdgcn_ballot_w64(ne) == 0;
+    auto at = [&](int i) { return flat ? 0.0f : x[i]; };
     float s = 0.0f;
-    for (int i = lane; i < n; i += 64) s += x[i];
+    for (int i = lane; i < n; i += 64) s += at(i);
     const float mean = wave_sum(s) / (float)n;
     float q = 0.0f;
     for (int i = lane; i < n; i += 64) {
-      const float d = x[i] - mean;
+      const float d = at(i) - mean;
       q = __builtin_fmaf(d, d, q);
     }
     float sd = sqrtf(wave_sum(q) / (float)(n - 1));
     sd = sd == 0.0f ? 1.0f : sd;
-    for (int i = lane; i < n; i += 64) y[i] = (x[i] - mean) / (sd + 1e-8f);
+    for (int i = lane; i < n; i += 64) y[i] = (at(i) - mean) / (sd + 1e-8f);
   } else if (method == 1) {  // minmax
     float mn = INFINITY, mx = -INFINITY;
     for (int i = lane; i < n; i += 64) {
