@@ -19,6 +19,13 @@ Timings are medians over the timed passes (HIP events on the current stream):
   torch_gpu          zero_grad, forward, F.ctc_loss, backward, clip_grad_norm_, Adam.step.
 
 Prints one JSON line and writes it to --out (profiles/ctc_train_bench.json).
+
+--dropout P runs another measurement instead and leaves the one above alone:
+CTCTrainer.step with both dropouts at P and with dropout off, on one handle
+(the trainer's dropout switched between passes), passes alternating, both
+really training; plus the no-dropout step's own min..max spread, which is
+what the difference has to be read against.  It writes
+profiles/ctc_dropout_bench.json (or --out).
 """
 import argparse
 import json
@@ -119,19 +126,66 @@ def bench_shape(name, B, T, V, S, iters, warmup, cpu_iters):
     return res
 
 
+def bench_dropout_shape(name, B, T, V, S, p, iters, warmup):
+    import torch
+    import wakeword
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(23)
+    feats = torch.randn((B, T, 80), generator=g).to(dev)
+    lab32 = torch.randint(1, V, (B, S), generator=g, dtype=torch.int64).to(dev, torch.int32)
+    il32 = torch.full((B,), T, dtype=torch.int32, device=dev)
+    tl32 = torch.full((B,), S, dtype=torch.int32, device=dev)
+    trainer = wakeword.CTCTrainer(torch_module(V, 5).state_dict(), V, max_norm=MAX_NORM, seed=23)
+    legs = {"wk_step": (0.0, 0.0), "wk_step_dropout": (p, p)}
+    times = {k: [] for k in legs}
+    values = {}
+    for i in range(warmup + iters):
+        for k, pair in legs.items():         # alternating passes on the one handle
+            trainer.dropout = pair
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            loss = trainer.step(feats, lab32, il32, tl32)
+            e1.record()
+            e1.synchronize()
+            if i >= warmup:
+                times[k].append(e0.elapsed_time(e1))
+            values[k] = {"last_loss": float(loss), "last_grad_norm": float(trainer._last[1])}
+    m0, m1 = trainer.model.dropout_masks()   # (of the last pass: the dropout leg's)
+    rows = B * T
+    res = {"shape": {"B": B, "T": T, "V": V, "S": S}, "iters": iters, "dropout": p, "values": values,
+           "kept_share": {"enc": float(m0.float().mean()), "gru": float(m1.float().mean())},
+           # forward: x0 read + written, y0 read, its dropped copy written; backward: both gradients read + written
+           "mask_traffic_bytes": 4 * rows * (2 * 128 + 2 * 256) * 2,
+           "ms_median": {k: statistics.median(v) for k, v in times.items()},
+           "ms_min": {k: min(v) for k, v in times.items()}, "ms_max": {k: max(v) for k, v in times.items()}}
+    res["dropout_minus_plain_ms"] = res["ms_median"]["wk_step_dropout"] - res["ms_median"]["wk_step"]
+    res["plain_spread_ms"] = res["ms_max"]["wk_step"] - res["ms_min"]["wk_step"]
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--cpu-iters", type=int, default=2)
     ap.add_argument("--shapes", default="reference,b64")
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "ctc_train_bench.json"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--dropout", type=float, default=None, metavar="P",
+                    help="time CTCTrainer.step with both dropouts at P against dropout off, on one handle")
     a = ap.parse_args()
+    if a.dropout is not None and not 0.0 < a.dropout < 1.0:
+        ap.error("--dropout takes a probability in (0, 1)")
+    if a.out is None:
+        a.out = os.path.join(REPO, "profiles", "ctc_dropout_bench.json" if a.dropout is not None else "ctc_train_bench.json")
     import torch
     if not torch.cuda.is_available():
         sys.exit("bench_ctc_train.py needs a HIP device")
-    out = {"bench": "ctc_train", "device": torch.cuda.get_device_name(0), "torch": torch.__version__,
-           "shapes": {n: bench_shape(n, *SHAPES[n], a.iters, a.warmup, a.cpu_iters) for n in a.shapes.split(",")}}
+    if a.dropout is not None:
+        out = {"bench": "ctc_dropout", "device": torch.cuda.get_device_name(0), "torch": torch.__version__,
+               "shapes": {n: bench_dropout_shape(n, *SHAPES[n], a.dropout, a.iters, a.warmup) for n in a.shapes.split(",")}}
+    else:
+        out = {"bench": "ctc_train", "device": torch.cuda.get_device_name(0), "torch": torch.__version__,
+               "shapes": {n: bench_shape(n, *SHAPES[n], a.iters, a.warmup, a.cpu_iters) for n in a.shapes.split(",")}}
     line = json.dumps(out)
     with open(a.out, "w") as f:
         f.write(line + "\n")

@@ -12,7 +12,8 @@
 // sequence of wk_ctc_features / wk_ctc_forward / wk_ctc_transcribe, which
 // call the launchers declared in wk_ctc_dev.h; and, for training, the fp32
 // forward that keeps its activations (wk_ctc_forward_train), the entry to
-// the backward pass of wk_ctc_bwd.hip (wk_ctc_backward), and the optimiser's
+// the backward pass of wk_ctc_bwd.hip (wk_ctc_backward), train-mode dropout over
+// wk_ctc_dropout.hip (wk_ctc_forward_train_dropout, wk_ctc_dropout_masks), and the optimiser's
 // entry points over wk_ctc_optim.hip (wk_ctc_adam_step, wk_ctc_weights,
 // wk_ctc_set_weights, wk_ctc_optim_state, wk_ctc_set_optim_state).
 #include <stdlib.h>
@@ -79,6 +80,10 @@ struct wk_ctc {
   DevBuf<float> tn_hprev, tn_dya, tn_dyb, tn_gh, tn_dai, tn_dah, tn_coef, tn_pre, tn_t0, tn_t1, tn_part;
   int64_t tn_batch;     // geometry of the last wk_ctc_forward_train (wk_ctc_backward)
   int32_t tn_T;
+  // dropout of the last training forward (all off after a plain wk_ctc_forward_train), and site 1's output: the dropped
+  // copy of tn_y[0], tn_rows rows, allocated by the first forward with p_gru > 0
+  CtcDrop tn_drop;
+  DevBuf<float> tn_y0d;
   // optimiser (fp32 handles; wk_ctc_adam_step): Adam's moments in blob order and the norm computed when the caller
   // passes none, allocated and zeroed on first use; the step count is host state
   DevBuf<float> opt_m, opt_v, opt_norm;
@@ -155,6 +160,7 @@ std::array<WsBuf, 18> tn_table(wk_ctc* c) {
 hipError_t alloc_tn(wk_ctc* c, size_t rows) {
   c->tn_rows = 0;
   c->tn_batch = 0;
+  c->tn_y0d.reset();   // (sized with the rest: the next forward that needs it allocates it again)
   for (const WsBuf& b : tn_table(c)) b.buf->reset();
   hipError_t e = hipSuccess;
   for (const WsBuf& b : tn_table(c))
@@ -543,12 +549,15 @@ wk_status wk_ctc_frame_argmax(wk_ctc* c, int64_t batch, int32_t T, int32_t* d_pr
   });
 }
 
-wk_status wk_ctc_forward_train(wk_ctc* c, const float* d_feats, int64_t batch, int32_t T, float* d_log_probs,
-                               void* stream) {
+namespace {
+// wk_ctc_forward_train, and with drop (validated) wk_ctc_forward_train_dropout: a site that is on adds one launch.
+wk_status ctc_forward_train(wk_ctc* c, const float* d_feats, int64_t batch, int32_t T, const wk_ctc_dropout* drop_or_null,
+                            float* d_log_probs, void* stream) {
   if (!c || !d_feats || !d_log_probs || batch <= 0 || T <= 0) return invalid("wk_ctc_forward_train: bad arguments");
   const int64_t rows = batch <= INT32_MAX ? batch * (int64_t)T : INT64_MAX;
   if (rows > INT32_MAX) return invalid("wk_ctc_forward_train: batch x frames exceeds 2^31 rows");
   if (c->f16) return fail(WK_ERR_UNSUPPORTED, "wk_ctc_forward_train: fp32 handles only (precision 0)");
+  const CtcDrop drop = drop_or_null ? ctc_drop(*drop_or_null) : CtcDrop{};
   return on_device(c->cfg.device, [&]() -> wk_status {
     hipStream_t st = (hipStream_t)stream;
     hipError_t e;
@@ -558,16 +567,25 @@ wk_status wk_ctc_forward_train(wk_ctc* c, const float* d_feats, int64_t batch, i
         return e == hipErrorOutOfMemory ? WK_ERR_NO_MEMORY : hip_fail(e, "wk_ctc_forward_train workspace");
     }
     c->tn_batch = 0;   // (set once every stage is enqueued)
+    if (drop.on[1] && !c->tn_y0d) {
+      if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(e, "sync");
+      if ((e = c->tn_y0d.alloc(c->tn_rows * 2 * kH)) != hipSuccess)
+        return e == hipErrorOutOfMemory ? WK_ERR_NO_MEMORY : hip_fail(e, "wk_ctc_forward_train_dropout workspace");
+    }
     const int H = kH, V = c->cfg.vocab;
     if ((e = hipMemcpyAsync(c->tn_feats, d_feats, sizeof(float) * rows * kMels, hipMemcpyDeviceToDevice, st)) != hipSuccess)
       return hip_fail(e, "hipMemcpyAsync");
     // wk_ctc_forward's fp32 stages, kernel for kernel, on the training buffers
     launch_ctc_encoder(false, d_feats, (int)batch, T, c->enc_w, c->enc_b, c->ln_g, c->ln_b, nullptr, c->tn_x0.get(), c->n_cu, st);
+    // site 0 in place: the backward's ReLU mask x0 > 0 holds for the dropped x0 (a kept positive stays positive)
+    if (drop.on[0]) launch_ctc_dropout_fwd(drop, 0, c->tn_x0.get(), c->tn_x0.get(), rows, c->n_cu, st);
     for (int l = 0; l < 2; ++l) {
-      const wk_status s = ctc_gemm_nt(st, rows, 6 * H, l == 0 ? H : 2 * H, l == 0 ? c->tn_x0.get() : c->tn_y[0].get(), c->wih[l],
-                                      c->tn_gi[l].get(), false);
+      // layer 1 reads the dropped copy of y0; tn_y[0] stays undropped, layer 0's h_prev in the backward
+      const float* x = l == 0 ? c->tn_x0.get() : drop.on[1] ? c->tn_y0d.get() : c->tn_y[0].get();
+      const wk_status s = ctc_gemm_nt(st, rows, 6 * H, l == 0 ? H : 2 * H, x, c->wih[l], c->tn_gi[l].get(), false);
       if (s != WK_OK) return s;
       launch_ctc_gru(false, c->tn_gi[l].get(), c->whh_pk[l].get(), c->bih[l], c->bhh[l], batch, T, c->tn_y[l].get(), st);
+      if (l == 0 && drop.on[1]) launch_ctc_dropout_fwd(drop, 1, c->tn_y[0].get(), c->tn_y0d.get(), rows, c->n_cu, st);
     }
     const wk_status s = ctc_gemm_nt(st, rows, V, 2 * H, c->tn_y[1].get(), c->out_w, c->tn_logits.get(), false);
     if (s != WK_OK) return s;
@@ -576,7 +594,36 @@ wk_status wk_ctc_forward_train(wk_ctc* c, const float* d_feats, int64_t batch, i
     if (e != hipSuccess) return hip_fail(e, "wk_ctc_forward_train launch");
     c->tn_batch = batch;
     c->tn_T = T;
+    c->tn_drop = drop;
     return WK_OK;
+  });
+}
+}  // namespace
+
+wk_status wk_ctc_forward_train(wk_ctc* c, const float* d_feats, int64_t batch, int32_t T, float* d_log_probs,
+                               void* stream) {
+  return ctc_forward_train(c, d_feats, batch, T, nullptr, d_log_probs, stream);
+}
+
+wk_status wk_ctc_forward_train_dropout(wk_ctc* c, const float* d_feats, int64_t batch, int32_t T,
+                                       const wk_ctc_dropout* drop, float* d_log_probs, void* stream) {
+  if (!drop) return invalid("wk_ctc_forward_train_dropout: null drop");
+  for (const float p : {drop->p_enc, drop->p_gru})
+    if (!(p >= 0.0f && p < 1.0f)) return invalid("wk_ctc_forward_train_dropout: p_enc and p_gru must lie in [0, 1)");
+  if (drop->offset >> 63) return invalid("wk_ctc_forward_train_dropout: offset must be < 2^63");
+  return ctc_forward_train(c, d_feats, batch, T, drop, d_log_probs, stream);
+}
+
+wk_status wk_ctc_dropout_masks(wk_ctc* c, uint8_t* d_mask_enc_or_null, uint8_t* d_mask_gru_or_null, void* stream) {
+  if (!c) return invalid("wk_ctc_dropout_masks: null handle");
+  if (c->f16) return fail(WK_ERR_UNSUPPORTED, "wk_ctc_dropout_masks: fp32 handles only (precision 0)");
+  if (c->tn_batch <= 0) return invalid("wk_ctc_dropout_masks: no training forward on this handle yet");
+  return on_device(c->cfg.device, [&]() -> wk_status {
+    uint8_t* const out[2] = {d_mask_enc_or_null, d_mask_gru_or_null};
+    for (int s = 0; s < 2; ++s)
+      if (out[s]) launch_ctc_dropout_mask(c->tn_drop, s, out[s], c->tn_batch * (int64_t)c->tn_T, c->n_cu, (hipStream_t)stream);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? WK_OK : hip_fail(e, "wk_ctc_dropout_masks launch");
   });
 }
 
@@ -595,6 +642,8 @@ wk_status wk_ctc_backward(wk_ctc* c, int64_t batch, int32_t T, const float* d_dl
     a.n_cu = c->n_cu;
     a.feats = c->tn_feats;
     a.x0 = c->tn_x0;
+    a.x1 = c->tn_drop.on[1] ? c->tn_y0d : c->tn_y[0];
+    a.drop = c->tn_drop;
     a.enc_w = c->enc_w;
     a.enc_b = c->enc_b;
     a.ln_g = c->ln_g;

@@ -481,7 +481,7 @@ void launch_ctc_backward(const CtcBwd& a, hipStream_t st) {
   gemm(st, (int)rows, 2 * H, V, {a.dlogits, V, 1}, {a.out_w, 1, 2 * H}, a.dya, 2 * H, part);
   for (int l = 1; l >= 0; --l) {
     const int din = l == 0 ? H : 2 * H;
-    const float* x = l == 0 ? a.x0 : a.y[0];
+    const float* x = l == 0 ? a.x0 : a.x1;
     const float* dy = l == 1 ? a.dya : a.dyb;
     float* dx = l == 1 ? a.dyb : a.dya;
     hipLaunchKernelGGL(ctc_bwd_shift_kernel, dim3(grid_for(rows * (2 * H / 4), a.n_cu)), dim3(256), 0, st, a.y[l], rows, a.T,
@@ -501,6 +501,8 @@ void launch_ctc_backward(const CtcBwd& a, hipStream_t st) {
     }
     // dx = da_i [rows][fwd 384 | rev 384] W_ih [fwd rows; rev rows]: both directions' shares in one product
     gemm(st, (int)rows, din, 6 * H, {a.da_i, 6 * H, 1}, {a.wih[l], 1, din}, dx, din, part);
+    // the layer's input went through dropout site l: dx <- s m dx (site 0: x0 > 0 below already implies m; s is still due)
+    if (a.drop.on[l]) launch_ctc_dropout_bwd(a.drop, l, dx, rows, a.n_cu, st);
   }
   // encoder (dx0 = a.dya [rows][128])
   gemm(st, (int)rows, H, kMels, {a.feats, kMels, 1}, {a.enc_w, kMels, 1}, a.pre, H, part);

@@ -6,6 +6,7 @@
 //   wk_ctc_dense.hip   X2a  encoder (fp32 / fp16), the block GEMM, fp16 <-> fp32 copy
 //   wk_ctc_gru.hip     X2b  the three recurrences and their weight packers
 //   wk_ctc_out.hip     X2c / X3  output layer + argmax kernels, re-score, greedy decode
+//   wk_ctc_dropout.hip train-mode dropout: Philox masks applied in the forward, made again in the backward
 //   wk_ctc_bwd.hip     the fp32 backward pass: parameter gradients from the gradient at the logits
 //   wk_ctc_optim.hip   clip + Adam on the handle's weights, the W_hh fragments again, blob <-> buffers
 //
@@ -117,6 +118,25 @@ void launch_ctc_rescore(const __half* y, const float* w, const float* bias, int6
 void launch_ctc_greedy(const int* best, int64_t B, int T, int* tokens, int* lengths, int tm, hipStream_t st);
 void launch_ctc_pred(const int* best, int64_t B, int T, int tm, int* pred, hipStream_t st);
 
+// ---- wk_ctc_dropout.hip -----------------------------------------------------
+// Train-mode dropout as wakeword.h states it.  Site 0: the encoder output
+// [rows][128]; site 1: layer 0's output as layer 1's input [rows][256].  on[s]
+// false (p = 0): the site is the identity and nothing is launched for it.
+constexpr int kCtcDropWidth[2] = {kH, 2 * kH};
+struct CtcDrop {
+  uint64_t seed, offset;
+  uint32_t thr[2];   // kept iff the element's Philox word >= thr
+  float scale[2];    // 1.0f / (1.0f - p)
+  bool on[2];
+};
+CtcDrop ctc_drop(const wk_ctc_dropout& d);
+// out = scale * mask * in over [rows][width of site]; in == out is allowed.
+void launch_ctc_dropout_fwd(const CtcDrop& d, int site, const float* in, float* out, int64_t rows, int n_cu, hipStream_t st);
+// dx <- scale * mask * dx, in place: the same mask made again.
+void launch_ctc_dropout_bwd(const CtcDrop& d, int site, float* dx, int64_t rows, int n_cu, hipStream_t st);
+// mask [rows][width of site] bytes, 1 = kept (all ones for a site that is off).
+void launch_ctc_dropout_mask(const CtcDrop& d, int site, uint8_t* mask, int64_t rows, int n_cu, hipStream_t st);
+
 // ---- wk_ctc_bwd.hip ---------------------------------------------------------
 // W_hh [2 dir][384][128] fp32 -> ctc_gru_bptt_kernel's fragments of W_hh^T ([2][8 unit tiles][96 k-steps][64 lanes]).
 std::vector<float> ctc_pack_whht(const float* whh);
@@ -128,10 +148,15 @@ size_t ctc_bwd_part_floats(int V, int64_t rows);
 // [2][384][128], bih / bhh [768]).  Scratch: hprev, dya, dyb [rows][256]; gh,
 // da_i, da_h [rows][768]; coef [rows][1280]; pre, t0, t1 [rows][128]; part.
 // grads: the parameter blob's layout; norm (or null): its 2-norm.
+// Dropout (drop.on[s]; all off when zero-initialised): x0 is then the dropped
+// encoder output (masked in place by the forward), x1 is layer 1's input -- the
+// dropped copy of y[0], or y[0] itself with site 1 off -- and y[0] stays the
+// undropped output, layer 0's h_prev.
 struct CtcBwd {
   int64_t B;
   int T, V, n_cu;
-  const float *feats, *x0, *gi[2], *y[2];
+  const float *feats, *x0, *x1, *gi[2], *y[2];
+  CtcDrop drop;
   const float *enc_w, *enc_b, *ln_g, *wih[2], *whh[2], *whht_pk[2], *bih[2], *bhh[2], *out_w;
   float *hprev, *dya, *dyb, *gh, *da_i, *da_h, *coef, *pre, *t0, *t1, *part;
   size_t part_floats;   // of part: ctc_bwd_part_floats(V, rows), or more

@@ -36,7 +36,8 @@ EXPORTS = ("wk_create", "wk_destroy", "wk_mfcc", "wk_cnn", "wk_forward", "wk_syn
            "wk_trainer_grad", "wk_trainer_step", "wk_trainer_weights", "wk_quant_spec_default", "wk_set_quant",
            "wk_get_quant", "wk_quant_weights", "wk_calibrate_workspace_bytes", "wk_calibrate",
            "wk_ctc_loss_workspace_bytes", "wk_ctc_loss", "wk_ctc_forward_train", "wk_ctc_backward", "wk_ctc_weights",
-           "wk_ctc_set_weights", "wk_ctc_adam_step", "wk_ctc_optim_state", "wk_ctc_set_optim_state")
+           "wk_ctc_set_weights", "wk_ctc_adam_step", "wk_ctc_optim_state", "wk_ctc_set_optim_state",
+           "wk_ctc_forward_train_dropout", "wk_ctc_dropout_masks")
 WK_CTC_REDUCTION = {"none": 0, "sum": 1, "mean": 2}
 WK_NUM_INT8_WEIGHTS = 3 * 13 * 32 + 3 * 32 * 64 + 3 * 64 * 128 + 128 * 64 + 64
 WK_QUANT_TENSORS = 7
@@ -62,6 +63,10 @@ class WkAdamW(C.Structure):
 class WkCtcAdam(C.Structure):
     _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
                 ("weight_decay", C.c_float), ("max_norm", C.c_float)]
+
+
+class WkCtcDropout(C.Structure):
+    _fields_ = [("p_enc", C.c_float), ("p_gru", C.c_float), ("seed", C.c_uint64), ("offset", C.c_uint64)]
 
 
 class WkQuantSpec(C.Structure):
@@ -166,6 +171,11 @@ def _declare(L):
         for name in ("wk_ctc_weights", "wk_ctc_set_weights", "wk_ctc_adam_step", "wk_ctc_optim_state",
                      "wk_ctc_set_optim_state"):
             getattr(L, name).restype = i32
+    if hasattr(L, "wk_ctc_forward_train_dropout"):
+        L.wk_ctc_forward_train_dropout.argtypes = [vp, vp, i64, i32, C.POINTER(WkCtcDropout), vp, vp]
+        L.wk_ctc_forward_train_dropout.restype = i32
+        L.wk_ctc_dropout_masks.argtypes = [vp, vp, vp, vp]
+        L.wk_ctc_dropout_masks.restype = i32
     for name in ("wk_create", "wk_destroy", "wk_mfcc", "wk_cnn", "wk_forward", "wk_synth_clips", "wk_normalize",
                  "wk_stream_create", "wk_stream_destroy", "wk_stream_reset", "wk_stream_push", "wk_ctc_create",
                  "wk_ctc_destroy", "wk_ctc_features", "wk_ctc_forward", "wk_wav_read", "wk_wav_load_batch",

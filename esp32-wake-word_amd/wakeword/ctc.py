@@ -262,6 +262,18 @@ class CTCLoss:
     __call__ = forward
 
 
+def dropout_pair(dropout) -> Tuple[float, float]:
+    """`dropout` as (p_enc, p_gru): None is (0, 0), a float both sites, a pair
+    itself.  wk_ctc_forward_train_dropout's rule, raised before any device
+    work: each p in [0, 1)."""
+    if dropout is None:
+        return 0.0, 0.0
+    pair = tuple(dropout) if isinstance(dropout, (tuple, list)) else (dropout, dropout)
+    if len(pair) != 2 or not all(isinstance(p, (int, float)) and not isinstance(p, bool) and 0.0 <= p < 1.0 for p in pair):
+        raise ValueError(f"dropout must be a probability in [0, 1) or a pair of them, got {dropout!r}")
+    return float(pair[0]), float(pair[1])
+
+
 class CTCModel:
     def __init__(self, weights: Union[np.ndarray, Mapping[str, np.ndarray]], vocab: int, device: int = 0,
                  precision: str = "fp32", idx_to_char: Optional[Mapping[int, str]] = None):
@@ -373,18 +385,47 @@ class CTCModel:
         return ctc_loss(lp, targets, input_lengths, target_lengths, reduction=reduction, batch_first=True)
 
     # ---- parameter gradients (fp32 models; wk_ctc_forward_train / wk_ctc_backward) ----
-    def forward_train(self, feats):
-        """(B, T, 80) -> (B, T, V) log-probs on the device, bit for bit those
-        of decode(..., return_log_probs=True), with the activations backward()
-        needs kept in the model's training workspace.  The eval-mode function
-        (no dropout); no tokens are decoded."""
+    def forward_train(self, feats, dropout=None, seed: int = 0, offset: int = 0):
+        """(B, T, 80) -> (B, T, V) log-probs on the device, with the
+        activations backward() needs kept in the model's training workspace;
+        no tokens are decoded.  Dropout is off by default: the eval-mode
+        function, bit for bit decode(..., return_log_probs=True).  `dropout`
+        (a probability for both sites, or (p_enc, p_gru); the reference
+        trains at 0.2, ctc.py:34) applies the train-mode masks of
+        wk_ctc_forward_train_dropout, a function of (seed, offset) alone:
+        pass a new offset per step.  backward() differentiates whichever
+        function the last forward_train computed."""
         import torch
+        p_enc, p_gru = dropout_pair(dropout)
+        if not 0 <= int(seed) < 2 ** 64 or not 0 <= int(offset) < 2 ** 63:
+            raise ValueError(f"seed must lie in [0, 2^64) and offset in [0, 2^63), got {seed!r}, {offset!r}")
         f = torch.as_tensor(feats, dtype=torch.float32).to(f"cuda:{self.device}").contiguous()
         B, T, _ = f.shape
         lp = torch.empty((B, T, self.vocab), dtype=torch.float32, device=f.device)
-        check(lib().wk_ctc_forward_train(self._h, C.c_void_p(f.data_ptr()), B, T, C.c_void_p(lp.data_ptr()),
-                                         self._stream(torch)), "wk_ctc_forward_train")
+        if dropout is None:
+            check(lib().wk_ctc_forward_train(self._h, C.c_void_p(f.data_ptr()), B, T, C.c_void_p(lp.data_ptr()),
+                                             self._stream(torch)), "wk_ctc_forward_train")
+        else:
+            drop = _lib.WkCtcDropout(p_enc, p_gru, int(seed), int(offset))
+            check(lib().wk_ctc_forward_train_dropout(self._h, C.c_void_p(f.data_ptr()), B, T, C.byref(drop),
+                                                     C.c_void_p(lp.data_ptr()), self._stream(torch)),
+                  "wk_ctc_forward_train_dropout")
+        self._train_shape = (B, T)
         return lp
+
+    def dropout_masks(self):
+        """The masks of the last forward_train as two bool device tensors
+        (True = kept): (B, T, 128) for the encoder output and (B, T, 256) for
+        layer 0's output as layer 1's input; all True for a site that was off."""
+        import torch
+        if getattr(self, "_train_shape", None) is None:
+            raise ValueError("no forward_train on this model yet")
+        B, T = self._train_shape
+        enc = torch.empty((B, T, 128), dtype=torch.uint8, device=f"cuda:{self.device}")
+        gru = torch.empty((B, T, 256), dtype=torch.uint8, device=f"cuda:{self.device}")
+        check(lib().wk_ctc_dropout_masks(self._h, C.c_void_p(enc.data_ptr()), C.c_void_p(gru.data_ptr()), self._stream(torch)),
+              "wk_ctc_dropout_masks")
+        return enc.bool(), gru.bool()
 
     def backward(self, dlogits, return_norm: bool = False):
         """The gradient of every parameter as one flat float32 device tensor in
@@ -407,22 +448,24 @@ class CTCModel:
         return (out, norm.reshape(())) if return_norm else out
 
     def loss_and_grad(self, feats, targets, input_lengths, target_lengths, reduction: str = "mean",
-                      zero_infinity: bool = False):
+                      zero_infinity: bool = False, dropout=None, seed: int = 0, offset: int = 0):
         """The loss half of a training step (ctc.py:390-401, without the clip
         and the optimiser): forward_train, wk_ctc_loss with its gradient
         output, backward.  Returns (loss, {state-dict key: gradient view},
         gradient 2-norm), all on the device; loss is per utterance for
-        reduction="none", whose gradient is that of the sum."""
-        loss, flat, norm = self._loss_and_flat_grad(feats, targets, input_lengths, target_lengths, reduction, zero_infinity)
+        reduction="none", whose gradient is that of the sum.  dropout, seed,
+        offset: forward_train's (off by default)."""
+        loss, flat, norm = self._loss_and_flat_grad(feats, targets, input_lengths, target_lengths, reduction, zero_infinity,
+                                                    dropout, seed, offset)
         return loss, unpack_grads(flat, self.vocab), norm
 
     def _loss_and_flat_grad(self, feats, targets, input_lengths, target_lengths, reduction: str = "mean",
-                            zero_infinity: bool = False):
+                            zero_infinity: bool = False, dropout=None, seed: int = 0, offset: int = 0):
         """loss_and_grad with the gradient as backward() returns it: one flat tensor."""
         import torch
         if reduction not in _lib.WK_CTC_REDUCTION:
             raise ValueError(f"reduction must be 'none', 'sum' or 'mean', got {reduction!r}")
-        lp = self.forward_train(feats)
+        lp = self.forward_train(feats, dropout, seed, offset)
         B, T, V = lp.shape
         labels = pad_targets(targets, target_lengths).to(lp.device).contiguous()
         in_len = torch.as_tensor(input_lengths).reshape(-1).to(device=lp.device, dtype=torch.int32).contiguous()

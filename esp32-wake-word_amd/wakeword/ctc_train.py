@@ -8,8 +8,10 @@ The reference builds ``nn.CTCLoss(blank=0)`` and ``optim.Adam(lr=1e-3)``
 with its gradient, BPTT, the clip and Adam are HIP kernels of libwakeword.so
 working on one ``wk_ctc`` handle, whose weights the step updates in place, so
 the same handle validates (``val_loss``) and decodes with the new weights.
-The function trained is the eval-mode one: the reference's two dropouts
-(ctc.py:131, :140) are not applied.
+Dropout is off by default (the function trained is then the eval-mode one);
+``dropout=0.2`` applies the reference's two train-mode dropouts (ctc.py:131,
+:140) as masks drawn from ``(seed, step)``, so a run is reproducible and
+resumable from ``rng_state()``.
 
     trainer = wakeword.CTCTrainer(model_or_state_dict_or_blob, vocab=V)
     loss = trainer.step(feats, labels, feat_lengths, label_lengths)   # 0-d device tensor, no host sync
@@ -23,7 +25,7 @@ from typing import Dict, Iterable, Mapping, Optional, Tuple
 
 import numpy as np
 
-from .ctc import CTCModel, _as_f32, pack_state_dict, unpack_grads
+from .ctc import CTCModel, _as_f32, dropout_pair, pack_state_dict, unpack_grads
 
 
 def check_hyper(lr, betas, eps, weight_decay, max_norm) -> None:
@@ -50,8 +52,10 @@ class CTCTrainer:
 
     def __init__(self, weights, vocab: int, device: int = 0, lr: float = 1e-3, betas: Tuple[float, float] = (0.9, 0.999),
                  eps: float = 1e-8, weight_decay: float = 0.0, max_norm: float = 5.0, zero_infinity: bool = False,
-                 idx_to_char: Optional[Mapping[int, str]] = None):
+                 idx_to_char: Optional[Mapping[int, str]] = None, dropout=0.0, seed: int = 0):
         check_hyper(lr, betas, eps, weight_decay, max_norm)
+        self.dropout = dropout_pair(dropout)     # (p_enc, p_gru); the reference trains at 0.2 (ctc.py:34)
+        self.load_rng_state(seed, 0)
         self.hyper = dict(lr=float(lr), betas=(float(betas[0]), float(betas[1])), eps=float(eps),
                           weight_decay=float(weight_decay), max_norm=float(max_norm))
         self.vocab, self.device, self.zero_infinity = vocab, device, bool(zero_infinity)
@@ -67,9 +71,13 @@ class CTCTrainer:
     def grad(self, feats, targets, input_lengths, target_lengths):
         """(B, T, 80) features, nn.CTCLoss's targets and lengths -> (mean CTC
         loss, the flat gradient in the blob's order, its 2-norm), on the
-        device; kept for apply()."""
+        device; kept for apply().  With dropout, the k-th call (from 0) draws
+        its masks at offset k under the trainer's seed."""
+        on = any(p > 0.0 for p in self.dropout)
         loss, flat, norm = self.model._loss_and_flat_grad(feats, targets, input_lengths, target_lengths, "mean",
-                                                          self.zero_infinity)
+                                                          self.zero_infinity, self.dropout if on else None, self._seed,
+                                                          self._offset)
+        self._offset += 1
         self._last = (flat, norm)
         return loss, flat, norm
 
@@ -90,8 +98,17 @@ class CTCTrainer:
         self.apply()
         return loss
 
+    def rng_state(self) -> Tuple[int, int]:
+        """(seed, offset): the dropout masks' seed and the number of grad() calls so far."""
+        return self._seed, self._offset
+
+    def load_rng_state(self, seed: int, offset: int) -> None:
+        if not 0 <= int(seed) < 2 ** 64 or not 0 <= int(offset) < 2 ** 63:
+            raise ValueError(f"seed must lie in [0, 2^64) and offset in [0, 2^63), got {seed!r}, {offset!r}")
+        self._seed, self._offset = int(seed), int(offset)
+
     def val_loss(self, feats, targets, input_lengths, target_lengths):
-        """The validation loss of ctc.py:409-425 at the current weights."""
+        """The validation loss of ctc.py:409-425 at the current weights: eval mode, no dropout."""
         return self.model.loss(feats, targets, input_lengths, target_lengths)
 
     def weights(self):
@@ -124,7 +141,9 @@ def train_ctc(train_loader: Iterable, val_loader: Iterable, vocab: int, num_epoc
 
     `trainer`: a CTCTrainer (or an object with step, val_loss and state_dict);
     built from `weights` -- default: torch's initialisation at seed 0 -- and
-    **hyper when None.  Returns (trainer, train_losses, val_losses, best_state_dict)."""
+    **hyper when None.  **hyper are CTCTrainer's keywords; among them
+    `dropout` (default 0: off; the reference trains at 0.2, ctc.py:34) and the
+    masks' `seed`.  Returns (trainer, train_losses, val_losses, best_state_dict)."""
     if trainer is None:
         if weights is None:
             from .ctc import random_state_dict

@@ -314,9 +314,11 @@ wk_status wk_ctc_frame_argmax(wk_ctc* c, int64_t batch, int32_t T, int32_t* d_pr
 
 /* ---- CTC head: parameter gradients (the backward half of ctc.py:380-407) -----
  * fp32 handles only (precision 0; a precision-1 handle: WK_ERR_UNSUPPORTED
- * before any device work).  The function differentiated is the one
- * wk_ctc_forward computes: the eval-mode module (no dropout is applied), as
- * CTCModel.loss uses it.  No optimiser step and no clipping are done here.
+ * before any device work).  The function differentiated is the one the
+ * handle's last training forward computed: with wk_ctc_forward_train, the one
+ * wk_ctc_forward computes (the eval-mode module, as CTCModel.loss uses it);
+ * dropout is off by default and on with wk_ctc_forward_train_dropout (below).
+ * No optimiser step and no clipping are done here.
  *
  * wk_ctc_forward_train: d_feats [batch][T][80] -> d_log_probs [batch][T][V],
  * bit for bit wk_ctc_forward's fp32 log-probs (the same kernels), and keeps in
@@ -347,6 +349,49 @@ wk_status wk_ctc_forward_train(wk_ctc* c, const float* d_feats, int64_t batch, i
                                void* stream);
 wk_status wk_ctc_backward(wk_ctc* c, int64_t batch, int32_t T, const float* d_dlogits, float* d_grads,
                           float* d_grad_norm_or_null, void* stream);
+
+/* ---- CTC head: train-mode dropout (ctc.py:131, :140; model.train(), ctc.py:382) ----
+ * The reference's two dropouts, as masks that are generated and never stored.
+ * Site 0 is the encoder's output after the ReLU, [batch*T][128] (nn.Dropout,
+ * ctc.py:131); site 1 is GRU layer 0's output where it is layer 1's input,
+ * [batch*T][256] (nn.GRU(dropout=), ctc.py:140; layer 0's own recurrence keeps
+ * the undropped output).  An element is kept with probability 1 - p and then
+ * multiplied by s = 1.0f / (1.0f - p) (computed in float), else set to 0.
+ *
+ * The mask is a function of (seed, offset, site, element) alone:
+ * Philox4x32-10 (multipliers D2511F53, CD9E8D57; key increments 9E3779B9,
+ * BB67AE85) with key = (seed low, seed high) and counter = (q low, q high,
+ * offset low, offset high | site << 31), where element e = row * width + unit,
+ * row = b * T + t, q = e / 4; element e takes output word e % 4 and is kept
+ * iff word >= (uint32) floor((double) p * 2^32).  So offset must be < 2^63.
+ * Use one offset per training forward (the step number) under one seed.
+ *
+ * wk_ctc_forward_train_dropout is wk_ctc_forward_train with the masks applied;
+ * p = 0 turns a site off (no kernel runs and no buffer is allocated for it),
+ * and with both at 0 it enqueues exactly what wk_ctc_forward_train does.  The
+ * handle records *drop as the dropout of its last training forward (a plain
+ * wk_ctc_forward_train records "none"), and wk_ctc_backward differentiates
+ * that function, making the same masks again.  Site 1 takes a second
+ * [batch*T][256] buffer, allocated on the first call with p_gru > 0 (the only
+ * other time, besides the workspace growth, that a call may block the host).
+ * seed and offset travel by value in the launch arguments: a captured graph
+ * replays the same mask every time, so a step captured once does not draw new
+ * masks -- re-capture, or leave dropout steps uncaptured.
+ *
+ * wk_ctc_dropout_masks makes the masks of the handle's last training forward
+ * again as bytes (1 = kept), [batch*T][128] and [batch*T][256]; either pointer
+ * may be NULL; a site that was off gives all ones.  For tests, and for
+ * reproducing a step elsewhere.
+ *
+ * WK_ERR_INVALID_ARG before any device work: a null drop; a p that is
+ * negative, >= 1 or NaN; offset >= 2^63; wk_ctc_forward_train's argument rules;
+ * wk_ctc_dropout_masks before any training forward.  WK_ERR_UNSUPPORTED: a
+ * precision-1 handle. */
+typedef struct { float p_enc, p_gru; uint64_t seed, offset; } wk_ctc_dropout;   /* ctc.py:34: 0.2, 0.2 */
+wk_status wk_ctc_forward_train_dropout(wk_ctc* c, const float* d_feats, int64_t batch, int32_t T,
+                                       const wk_ctc_dropout* drop, float* d_log_probs, void* stream);
+wk_status wk_ctc_dropout_masks(wk_ctc* c, uint8_t* d_mask_enc_or_null /* [batch*T][128] */,
+                               uint8_t* d_mask_gru_or_null /* [batch*T][256] */, void* stream);
 
 /* ---- CTC head: the optimiser (clip_grad_norm_ + optim.Adam; ctc.py:368, :401-402) ----
  * fp32 handles only (a precision-1 handle, and a handle created under
