@@ -16,6 +16,7 @@ from .ctc import (CTCLoss, CTCModel, ctc_loss, ctc_state_dict_spec, decode_predi
 from .ctc_train import CTCTrainer, train_ctc  # noqa: F401
 from .train import Trainer, train_model  # noqa: F401
 from .quant import QuantSpec, accuracy, calibrate, int8_weights, quantize_model  # noqa: F401
+from .augment import REFERENCE_VARIANTS, augment_batch, extract_features  # noqa: F401
 from . import wav  # noqa: F401
 
 LightweightKWS = KWSModel

@@ -37,12 +37,14 @@ EXPORTS = ("wk_create", "wk_destroy", "wk_mfcc", "wk_cnn", "wk_forward", "wk_syn
            "wk_get_quant", "wk_quant_weights", "wk_calibrate_workspace_bytes", "wk_calibrate",
            "wk_ctc_loss_workspace_bytes", "wk_ctc_loss", "wk_ctc_forward_train", "wk_ctc_backward", "wk_ctc_weights",
            "wk_ctc_set_weights", "wk_ctc_adam_step", "wk_ctc_optim_state", "wk_ctc_set_optim_state",
-           "wk_ctc_forward_train_dropout", "wk_ctc_dropout_masks")
+           "wk_ctc_forward_train_dropout", "wk_ctc_dropout_masks", "wk_augment_batch")
 WK_CTC_REDUCTION = {"none": 0, "sum": 1, "mean": 2}
 WK_NUM_INT8_WEIGHTS = 3 * 13 * 32 + 3 * 32 * 64 + 3 * 64 * 128 + 128 * 64 + 64
 WK_QUANT_TENSORS = 7
 WK_QUANT_BINS = 32
 WK_QUANT_CALIBRATE_INPUT = -2 ** 31
+WK_AUG_MAX_VARIANTS = 16
+WK_AUG_MAX_LEN = 16384
 
 
 class WkConfig(C.Structure):
@@ -67,6 +69,15 @@ class WkCtcAdam(C.Structure):
 
 class WkCtcDropout(C.Structure):
     _fields_ = [("p_enc", C.c_float), ("p_gru", C.c_float), ("seed", C.c_uint64), ("offset", C.c_uint64)]
+
+
+class WkAugVariant(C.Structure):
+    _fields_ = [("speed", C.c_float), ("volume", C.c_float)]
+
+
+class WkAugSpec(C.Structure):
+    _fields_ = [("pad_noise", C.c_float), ("snr_noise", C.c_float), ("snr_lo_db", C.c_float), ("snr_hi_db", C.c_float),
+                ("seed", C.c_uint64), ("epoch", C.c_uint32)]
 
 
 class WkQuantSpec(C.Structure):
@@ -176,6 +187,10 @@ def _declare(L):
         L.wk_ctc_forward_train_dropout.restype = i32
         L.wk_ctc_dropout_masks.argtypes = [vp, vp, vp, vp]
         L.wk_ctc_dropout_masks.restype = i32
+    if hasattr(L, "wk_augment_batch"):   # (absent from older libraries loaded for A/B timing)
+        L.wk_augment_batch.argtypes = [vp, i32, vp, i64, i32, i64, C.POINTER(WkAugVariant), i32, C.POINTER(WkAugSpec), i32,
+                                       vp, vp]
+        L.wk_augment_batch.restype = i32
     for name in ("wk_create", "wk_destroy", "wk_mfcc", "wk_cnn", "wk_forward", "wk_synth_clips", "wk_normalize",
                  "wk_stream_create", "wk_stream_destroy", "wk_stream_reset", "wk_stream_push", "wk_ctc_create",
                  "wk_ctc_destroy", "wk_ctc_features", "wk_ctc_forward", "wk_wav_read", "wk_wav_load_batch",

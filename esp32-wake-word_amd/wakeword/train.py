@@ -123,6 +123,20 @@ class Trainer:
         """(B, 16000) audio -> mode-B front-end (MFCC + CMVN, extract_mfcc.py:137-175) -> step."""
         return self.step(mfcc(audio, mode="torchaudio", cmvn=True, device=self.device), labels)
 
+    def step_augmented(self, audio, lengths, labels, epoch: int = 0, **augment_kwargs):
+        """(n, L) raw clips with their `lengths` (None = L) and (n,) labels ->
+        ``wakeword.augment.extract_features`` (pad, the K variants, optional SNR
+        noise, MFCC + CMVN; `augment_kwargs` are its is_noise, add_noise_to_pad,
+        augment_audio and seed) -> step on the n*K rows, clip i's label repeated
+        for its K variants.  A new `epoch` draws the noise afresh."""
+        from .augment import extract_features
+        torch = _torch()
+        feats, _ = extract_features(audio, lengths, epoch=epoch, device=self.device, **augment_kwargs)
+        y = _as_device(labels, torch.float32, feats.device).reshape(-1)
+        if y.numel() == 0 or feats.shape[0] % y.numel():
+            raise ValueError(f"{y.numel()} labels for {feats.shape[0]} augmented rows")
+        return self.step(feats, y.repeat_interleave(feats.shape[0] // y.numel()))
+
     def weights(self):
         """Current weights as one flat device tensor in blob order."""
         torch = _torch()

@@ -498,6 +498,64 @@ wk_status wk_wav_load_batch(const char* const* paths, int32_t n, int32_t pad_to,
 wk_status wk_augment(const float* in, int32_t n, float speed, float volume, float noise_level, uint32_t seed, float* out,
                      int32_t out_len);
 
+/* ---- Batched waveform augmentation on the device (extract_mfcc.py:7-45,
+ * :90-121, :157-169) -----------------------------------------------------------
+ * extract_features' waveform stage for n clips and K variants: pad_audio, the
+ * speed / volume variants of augment_audio_waveform and add_random_noise, one
+ * workgroup per output row.  d_out[(i*K + v)][out_len], clip-major as the
+ * reference appends them; all arithmetic fp32.  Output row r = i*K + v:
+ *   1. pad / trim: a[j] = x_i[j] for j < min(len_i, out_len), else pad_noise *
+ *      g(0, i, j) (0 when pad_noise == 0).  The stream is keyed by the CLIP, so
+ *      all K variants see the same padded clip, as in the reference.
+ *   2. speed != 1: m = (int)((double)out_len * speed), scale = (float)out_len /
+ *      (float)m; j < m: src = max(scale*(j + 0.5f) - 0.5f, 0), i0 = (int)src, i1 =
+ *      i0 + (i0 < out_len-1), l1 = src - i0, l0 = 1 - l1, b[j] = l0*a[i0] + l1*a[i1]
+ *      (each product and the sum rounded on its own: with no noise the row is
+ *      bit-equal to wk_augment's); j >= m: b[j] = pad_noise * g(1, r, j).
+ *      speed == 1: b = a.
+ *   3. volume != 1: b = clamp(b * volume, -1, 1) (the pad included, as wk_augment).
+ *   4. snr_noise > 0 (add_random_noise as written, its amplitude ratio applied
+ *      to powers included): z[j] = snr_noise * g(2, r, j); u = (w >> 8) 2^-24 of
+ *      word 0 of block 0 of stream 3, row r; snr = 10^((lo + u (hi - lo)) / 20);
+ *      Ps = mean(b^2), Pn = mean(z^2) over out_len; z *= sqrt(Ps / (Pn snr)) when
+ *      Pn > 0; out = clamp(b + z, -1, 1).  The two means are reduced in a fixed
+ *      order without atomics: the same inputs give the same bits.
+ * Noise: g(stream, row, j) is sample j of the Philox4x32-10 stream with key =
+ * (seed low, seed high) and counter = (q, row, epoch, stream): block q gives
+ * samples 4q..4q+3, words (w0, w1) samples 4q and 4q+1, (w2, w3) samples 4q+2
+ * and 4q+3; for a pair (wa, wb): u1 = ((wa >> 8) + 1) 2^-24, u2 = (wb >> 8)
+ * 2^-24, rho = sqrt(-2 ln u1), the samples are rho cos(2 pi u2) and rho sin(2 pi
+ * u2).  Streams 1-3 are keyed by the output ROW, so a variant's noise depends
+ * on its position v in the list; a new `epoch` draws all noise afresh.
+ *
+ * No handle, no allocation, no host synchronisation; stream-ordered on the
+ * current device.  Clip i is at d_audio + i*in_stride elements (WK_DTYPE_F32,
+ * or WK_DTYPE_I16 scaled by 1/32768).  d_len_or_null[i] is the clip's length
+ * (NULL = in_len for all); it lives on the device and cannot be validated
+ * without a sync, so the kernel clamps it to [0, in_len] and never reads a
+ * clip past in_len.  d_out must not overlap d_audio; n*K must be below 2^32;
+ * row and sample offsets are 64-bit.
+ * WK_ERR_INVALID_ARG, before any device work: NULL d_audio, d_out, variants or
+ * spec; n < 0, in_len < 0, in_stride < in_len; n_variants outside [1,
+ * WK_AUG_MAX_VARIANTS]; a non-positive or non-finite speed or volume;
+ * (int)(out_len*speed) outside [1, 2^31); negative or non-finite noise levels;
+ * snr_lo_db > snr_hi_db or either non-finite; out_len outside [1,
+ * WK_AUG_MAX_LEN]; a dtype other than the two above; n*K >= 2^32.  n == 0 is
+ * WK_OK and launches nothing. */
+#define WK_AUG_MAX_VARIANTS 16
+#define WK_AUG_MAX_LEN 16384   /* one workgroup holds a row's b and z in LDS: 2 x 64 KiB */
+typedef struct { float speed, volume; } wk_aug_variant;   /* (1, 1) = the clip itself */
+typedef struct {
+  float    pad_noise;             /* pad_audio's noise_level (0.005); 0 = zero pad        */
+  float    snr_noise;             /* add_random_noise's noise_level (0.01); 0 = stage off */
+  float    snr_lo_db, snr_hi_db;  /* its snr_range (5, 20)                                */
+  uint64_t seed;                  /* Philox key                                           */
+  uint32_t epoch;                 /* a new value draws all noise afresh                   */
+} wk_aug_spec;
+wk_status wk_augment_batch(const void* d_audio, int32_t dtype, const int32_t* d_len_or_null, int64_t n, int32_t in_len,
+                           int64_t in_stride, const wk_aug_variant* variants, int32_t n_variants,
+                           const wk_aug_spec* spec, int32_t out_len, float* d_out, void* stream);
+
 /* ---- Training step (ml_models/main.py:13-64, train_model) --------------------
  * LightweightKWS(num_classes=1) under BCEWithLogitsLoss and AdamW, fp32.  A
  * wk_trainer owns the weights (blob order of WK_NUM_WEIGHTS), the last
