@@ -9,6 +9,8 @@ inference surface on the HIP path (wk_ctc_* in the C ABI).
     texts = model.transcribe_text(audio)                 # device decode, then the map
     loss = wakeword.ctc_loss(log_probs, targets, input_lengths, target_lengths)   # nn.CTCLoss(blank=0), ctc.py:369
     loss = model.loss(feats, targets, input_lengths, target_lengths)              # validation loss, ctc.py:409-425
+    al = wakeword.ctc_align(log_probs, targets, input_lengths, target_lengths)    # forced alignment: Alignment(states, tokens, ...)
+    al = model.align(feats, targets, target_lengths); model.align_audio(audio, targets, target_lengths); span_seconds(al.spans)
     loss, grads, norm = model.loss_and_grad(feats, targets, input_lengths, target_lengths)   # ctc.py:393-401, fp32
     lp = model.forward_train(feats); flat = model.backward(dlogits); grads = unpack_grads(flat, V)   # its pieces
     model.adam_step(grads, norm)                         # clip_grad_norm_(5.0) + Adam(lr=1e-3) in place, ctc.py:401-402
@@ -23,7 +25,7 @@ order (wk_ctc_create's layout, include/wakeword.h).
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, List, Mapping, Optional, Sequence, Tuple, Union
+from typing import Dict, List, Mapping, NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
@@ -262,6 +264,86 @@ class CTCLoss:
     __call__ = forward
 
 
+class Alignment(NamedTuple):
+    """ctc_align's result, device tensors: states (B, T) int32, the lattice
+    state per frame (0..2S, -1 past the input length or without an alignment);
+    tokens (B, T) int32, its label (0 = blank, -1 as states); frame_log_probs
+    (B, T) float32, that label's log-prob (0 where the state is -1); spans
+    (B, S_max, 2) int32, label i's frames [start, end) (-1 for i >= S or
+    without an alignment); scores (B,) float32, the path's log-probability
+    (-inf without an alignment)."""
+    states: object
+    tokens: object
+    frame_log_probs: object
+    spans: object
+    scores: object
+
+
+def _align_args(log_probs, targets, input_lengths, target_lengths, batch_first: bool):
+    """ctc_align's arguments as ctc_loss takes them -> (lp (B, T, V), labels,
+    in_len, lab_len, max_label_len), the tensors wk_ctc_align reads, on
+    log_probs' device."""
+    import torch
+    lp = (log_probs if batch_first else log_probs.transpose(0, 1)).detach().contiguous()
+    B = lp.shape[0]
+    labels = pad_targets(targets, target_lengths).to(lp.device).contiguous()
+    in_len = torch.as_tensor(input_lengths).reshape(-1).to(device=lp.device, dtype=torch.int32).contiguous()
+    lab_len = torch.as_tensor(target_lengths).reshape(-1).to(device=lp.device, dtype=torch.int32).contiguous()
+    if labels.shape[0] != B or in_len.numel() != B or lab_len.numel() != B:
+        raise ValueError(f"batch of {B}: targets {tuple(labels.shape)}, {in_len.numel()} input and {lab_len.numel()} target lengths")
+    max_label_len = labels.shape[1]
+    if max_label_len > MAX_LABEL_LEN:      # padding wider than the kernels' limit: the longest label decides (a host sync)
+        max_label_len = int(lab_len.max())
+    return lp, labels, in_len, lab_len, max_label_len
+
+
+def ctc_align(log_probs, targets, input_lengths, target_lengths, batch_first: bool = False) -> Alignment:
+    """CTC forced alignment on the HIP device (wk_ctc_align): the best path of
+    each utterance's known transcript through its log-probs, blank = 0 --
+    which frames every label occupies.  Arguments as ctc_loss: log_probs
+    (T, B, V) float32, or (B, T, V) with batch_first=True (used without a
+    copy); targets (B, S) padded or 1-D concatenated; lengths as tensors or
+    sequences.  Runs on the current stream, no host sync; the result is
+    defined bit for bit by the recurrence and tie rule in include/wakeword.h.
+    span_seconds converts the spans to time."""
+    import torch
+    if not (torch.is_tensor(log_probs) and log_probs.is_cuda and log_probs.dtype == torch.float32 and log_probs.dim() == 3):
+        raise ValueError("log_probs must be a 3-D float32 tensor on the HIP device")
+    lp, labels, in_len, lab_len, max_label_len = _align_args(log_probs, targets, input_lengths, target_lengths, batch_first)
+    B, T, V = lp.shape
+    L = lib()
+    nbytes = L.wk_ctc_align_workspace_bytes(B, T, max_label_len)
+    if nbytes <= 0:
+        raise _lib.WakewordError(f"wk_ctc_align: unsupported shape (B={B}, T={T}, max label length {max_label_len} "
+                                 f"> {MAX_LABEL_LEN}?)")
+    dev = lp.device
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)      # (the caching allocator's: no device malloc per call)
+    states = torch.empty((B, T), dtype=torch.int32, device=dev)
+    tokens = torch.empty((B, T), dtype=torch.int32, device=dev)
+    frame_lp = torch.empty((B, T), dtype=torch.float32, device=dev)
+    spans = torch.empty((B, max_label_len, 2), dtype=torch.int32, device=dev)
+    scores = torch.empty((B,), dtype=torch.float32, device=dev)
+
+    def ptr(t):
+        return C.c_void_p(t.data_ptr())
+    check(L.wk_ctc_align(ptr(lp), B, T, V, ptr(labels), labels.shape[1], ptr(in_len), ptr(lab_len), max_label_len, ptr(ws),
+                         ptr(states), ptr(tokens), ptr(frame_lp), ptr(spans), ptr(scores), dev.index,
+                         C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "wk_ctc_align")
+    return Alignment(states, tokens, frame_lp, spans, scores)
+
+
+def span_seconds(spans, hop: int = 160, sample_rate: int = 16000):
+    """Alignment.spans in seconds: frame t of the centred STFT sits on sample
+    t * hop, so label i covers [start * hop / sample_rate, end * hop /
+    sample_rate) -- 10 ms per frame at the defaults.  float64, a tensor for a
+    tensor and an array otherwise; rows without an alignment stay -1."""
+    if hasattr(spans, "detach"):
+        import torch
+        return torch.where(spans < 0, -1.0, spans.to(torch.float64) * hop / sample_rate)
+    s = np.asarray(spans)
+    return np.where(s < 0, -1.0, s.astype(np.float64) * hop / sample_rate)
+
+
 def dropout_pair(dropout) -> Tuple[float, float]:
     """`dropout` as (p_enc, p_gru): None is (0, 0), a float both sites, a pair
     itself.  wk_ctc_forward_train_dropout's rule, raised before any device
@@ -383,6 +465,21 @@ class CTCModel:
         return_log_probs=True), then ctc_loss on the (B, T, V) log-probs."""
         _, _, lp = self.decode(feats, return_log_probs=True)
         return ctc_loss(lp, targets, input_lengths, target_lengths, reduction=reduction, batch_first=True)
+
+    def align(self, feats, targets, target_lengths, input_lengths=None) -> Alignment:
+        """Forced alignment of known transcripts: decode(feats,
+        return_log_probs=True), then ctc_align on the (B, T, V) log-probs
+        (fp32 in an fp16 model too).  input_lengths: frames per utterance,
+        all T when None."""
+        _, _, lp = self.decode(feats, return_log_probs=True)
+        if input_lengths is None:
+            input_lengths = [lp.shape[1]] * lp.shape[0]
+        return ctc_align(lp, targets, input_lengths, target_lengths, batch_first=True)
+
+    def align_audio(self, audio, targets, target_lengths, n_samples: int = MAX_AUDIO_SAMPLES) -> Alignment:
+        """audio -> Alignment: features(), then align() over all T = 1 +
+        n_samples // 160 frames; span_seconds gives the labels' times."""
+        return self.align(self.features(audio, n_samples), targets, target_lengths)
 
     # ---- parameter gradients (fp32 models; wk_ctc_forward_train / wk_ctc_backward) ----
     def forward_train(self, feats, dropout=None, seed: int = 0, offset: int = 0):

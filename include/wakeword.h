@@ -473,6 +473,48 @@ wk_status wk_ctc_loss(const float* d_log_probs, int64_t batch, int32_t T, int32_
                       void* d_workspace, float* d_nll, float* d_loss, float* d_grad_or_null,
                       int32_t device, void* stream);
 
+/* ---- CTC forced alignment (Viterbi): which frames a known transcript occupies --
+ * Inputs as wk_ctc_loss: d_log_probs [batch][T][vocab] fp32, d_labels
+ * [batch][label_stride] int32, d_input_lengths / d_label_lengths [batch] int32
+ * on the device, clamped to [0, T] / [0, max_label_len].  Blank = 0; l' is the
+ * label sequence interleaved with blanks, L = 2S+1 states, Tb the clamped
+ * input length:
+ *   a_0(0) = lp_0(0),  a_0(1) = lp_0(l'_1),  a_0(s >= 2) = -inf
+ *   a_t(s) = lp_t(l'_s) + max(a_{t-1}(s), a_{t-1}(s-1), [a_{t-1}(s-2)])
+ * in fp32 with plain IEEE adds, the third term only for a label state whose
+ * label differs from the one two states back; score = max(a_{Tb-1}(L-1),
+ * a_{Tb-1}(L-2)), and the path follows the back-pointers from that state.
+ * Tie rule: among equal predecessors s, then s-1, then s-2 is preferred (a
+ * candidate replaces the best so far only if strictly greater); at the exit
+ * L-1, the trailing blank, when a(L-1) >= a(L-2).  max is exact and each add
+ * rounds once, so every output is defined bit for bit by the recurrence.
+ * Outputs:
+ *   d_states [batch][T]                 the state index s_t in 0..2S; -1 at t >= Tb
+ *   d_frame_tokens_or_null [batch][T]   l'_{s_t} (0 = blank); -1 where the state is
+ *   d_frame_lp_or_null [batch][T]       lp_t(l'_{s_t}), the input's bits; 0 where the state is -1
+ *   d_spans_or_null [batch][max_label_len][2]   label i occupies frames [start, end): the
+ *                                       one contiguous run with s_t = 2i+1; -1, -1 for i >= S
+ *   d_score [batch]                     the best path's log-probability
+ * No alignment -- a label outside [1, vocab) (never used as an index), Tb < S +
+ * the number of adjacent equal labels, Tb = 0, or every path through a -inf --
+ * gives score -inf, every state, token and span -1 and every frame_lp 0; the
+ * other utterances are unaffected.  S = 0: all blanks, state 0, the score is
+ * the sum of the blank column.  On NaN input the outputs are unspecified but
+ * every state stays in [0, L).
+ * Limits and argument checks are wk_ctc_loss's (max_label_len <= 255, vocab <=
+ * 65536, batch * T <= 2^28; null required pointers, non-positive sizes,
+ * label_stride < max_label_len, a workspace not 16-byte aligned:
+ * WK_ERR_INVALID_ARG before any device work; wk_ctc_align_workspace_bytes
+ * returns 0 beyond the limits).  Stream-ordered, no host synchronisation, no
+ * atomics; d_workspace is the caller's. */
+int64_t wk_ctc_align_workspace_bytes(int64_t batch, int32_t T, int32_t max_label_len);
+wk_status wk_ctc_align(const float* d_log_probs, int64_t batch, int32_t T, int32_t vocab,
+                       const int32_t* d_labels, int32_t label_stride,
+                       const int32_t* d_input_lengths, const int32_t* d_label_lengths, int32_t max_label_len,
+                       void* d_workspace, int32_t* d_states, int32_t* d_frame_tokens_or_null,
+                       float* d_frame_lp_or_null, int32_t* d_spans_or_null, float* d_score,
+                       int32_t device, void* stream);
+
 /* ---- WAV ingest and waveform augmentation (host only) ---
  * No device work: these fill caller (e.g. pinned) host buffers for the H2D copy. */
 typedef struct {
