@@ -11,6 +11,9 @@ inference surface on the HIP path (wk_ctc_* in the C ABI).
     loss = model.loss(feats, targets, input_lengths, target_lengths)              # validation loss, ctc.py:409-425
     al = wakeword.ctc_align(log_probs, targets, input_lengths, target_lengths)    # forced alignment: Alignment(states, tokens, ...)
     al = model.align(feats, targets, target_lengths); model.align_audio(audio, targets, target_lengths); span_seconds(al.spans)
+    res = wakeword.ctc_beam_search(log_probs, beam=16, top_k=16, n_best=4)        # prefix beam search: BeamResult(tokens, lengths, scores)
+    res = model.beam_decode(feats, beam=16); model.beam_decode_audio(audio, beam=16); beam_texts(res, idx_to_char)
+    tokens = model.transcribe(audio, beam=16)            # the best hypothesis of the beam instead of the greedy path
     loss, grads, norm = model.loss_and_grad(feats, targets, input_lengths, target_lengths)   # ctc.py:393-401, fp32
     lp = model.forward_train(feats); flat = model.backward(dlogits); grads = unpack_grads(flat, V)   # its pieces
     model.adam_step(grads, norm)                         # clip_grad_norm_(5.0) + Adam(lr=1e-3) in place, ctc.py:401-402
@@ -344,6 +347,92 @@ def span_seconds(spans, hop: int = 160, sample_rate: int = 16000):
     return np.where(s < 0, -1.0, s.astype(np.float64) * hop / sample_rate)
 
 
+MAX_BEAM = 64                   # wk_ctc_beam: one lane per beam slot
+MAX_TOP_K = 32                  # ... and one register per extension
+
+
+class BeamResult(NamedTuple):
+    """ctc_beam_search's result, device tensors, hypotheses in descending
+    order of score: tokens (B, n_best, max_len) int32, -1 beyond each length;
+    lengths (B, n_best) int32, the full length (it may exceed max_len; -1 for
+    a slot without a hypothesis); scores (B, n_best) float32, the log of the
+    summed probability of the hypothesis's paths the beam kept (-inf for an
+    empty slot); candidates (B, T, top_k) int32 if asked for, the per-frame
+    candidate tokens in descending log-prob (-1 past the input length)."""
+    tokens: object
+    lengths: object
+    scores: object
+    candidates: object = None
+
+
+def _beam_args(log_probs, input_lengths, beam, top_k, n_best, max_len, batch_first: bool):
+    """ctc_beam_search's arguments -> (lp (B, T, V), in_len or None, max_len),
+    what wk_ctc_beam reads, on log_probs' device; ValueError for what the
+    kernels do not take."""
+    import torch
+    for name, v, lo, hi in (("beam", beam, 1, MAX_BEAM), ("top_k", top_k, 1, MAX_TOP_K), ("n_best", n_best, 1, beam)):
+        if not isinstance(v, int) or isinstance(v, bool) or not lo <= v <= hi:
+            raise ValueError(f"{name} must be an integer in [{lo}, {hi}], got {v!r}")
+    lp = (log_probs if batch_first else log_probs.transpose(0, 1)).detach().contiguous()
+    B, T, V = lp.shape
+    if B < 1 or T < 1 or V < 2:
+        raise ValueError(f"log_probs (B, T, V) = {(B, T, V)}: B and T must be positive and V at least 2")
+    if max_len is None:
+        max_len = T
+    if not isinstance(max_len, int) or isinstance(max_len, bool) or max_len < 1:
+        raise ValueError(f"max_len must be a positive integer, got {max_len!r}")
+    in_len = None
+    if input_lengths is not None:
+        in_len = torch.as_tensor(input_lengths).reshape(-1).to(device=lp.device, dtype=torch.int32).contiguous()
+        if in_len.numel() != B:
+            raise ValueError(f"batch of {B}: {in_len.numel()} input lengths")
+    return lp, in_len, max_len
+
+
+def ctc_beam_search(log_probs, input_lengths=None, beam: int = 16, top_k: int = 16, n_best: int = 1,
+                    max_len: Optional[int] = None, batch_first: bool = False, return_candidates: bool = False) -> BeamResult:
+    """CTC prefix beam search on the HIP device (wk_ctc_beam): the n_best label
+    sequences of each utterance with the largest summed path probability, as
+    a beam of `beam` prefixes extended by the `top_k` most probable tokens of
+    each frame finds them (the algorithm is stated in include/wakeword.h).
+    log_probs (T, B, V) float32, or (B, T, V) with batch_first=True (used
+    without a copy); input_lengths as a tensor or sequence, all T when None;
+    max_len, the width of the token rows, defaults to T.  Runs on the current
+    stream, no host sync."""
+    import torch
+    if not (torch.is_tensor(log_probs) and log_probs.is_cuda and log_probs.dtype == torch.float32 and log_probs.dim() == 3):
+        raise ValueError("log_probs must be a 3-D float32 tensor on the HIP device")
+    lp, in_len, max_len = _beam_args(log_probs, input_lengths, beam, top_k, n_best, max_len, batch_first)
+    B, T, V = lp.shape
+    L = lib()
+    nbytes = L.wk_ctc_beam_workspace_bytes(B, T, beam, top_k)
+    if nbytes <= 0:
+        raise _lib.WakewordError(f"wk_ctc_beam: unsupported shape (B={B}, T={T}, beam={beam}, top_k={top_k})")
+    dev = lp.device
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)      # (the caching allocator's: no device malloc per call)
+    tokens = torch.empty((B, n_best, max_len), dtype=torch.int32, device=dev)
+    lengths = torch.empty((B, n_best), dtype=torch.int32, device=dev)
+    scores = torch.empty((B, n_best), dtype=torch.float32, device=dev)
+    cand = torch.empty((B, T, top_k), dtype=torch.int32, device=dev) if return_candidates else None
+
+    def ptr(t):
+        return C.c_void_p(t.data_ptr()) if t is not None else None
+    check(L.wk_ctc_beam(ptr(lp), B, T, V, ptr(in_len), beam, top_k, n_best, max_len, ptr(ws), ptr(tokens), ptr(lengths),
+                        ptr(scores), ptr(cand), dev.index, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "wk_ctc_beam")
+    return BeamResult(tokens, lengths, scores, cand)
+
+
+def beam_texts(result: BeamResult, idx_to_char: Mapping[int, str]) -> List[List[str]]:
+    """A BeamResult as text: per utterance the strings of its hypotheses in
+    order (tokens_to_text's mapping); slots without a hypothesis are left out,
+    a hypothesis longer than the token rows is cut there."""
+    tok, ln = result.tokens, result.lengths
+    tok = tok.cpu().numpy() if hasattr(tok, "cpu") else np.asarray(tok)
+    ln = ln.cpu().numpy() if hasattr(ln, "cpu") else np.asarray(ln)
+    return [tokens_to_text([tok[b, i, :min(int(ln[b, i]), tok.shape[2])].tolist() for i in range(tok.shape[1]) if ln[b, i] >= 0],
+                           idx_to_char) for b in range(tok.shape[0])]
+
+
 def dropout_pair(dropout) -> Tuple[float, float]:
     """`dropout` as (p_enc, p_gru): None is (0, 0), a float both sites, a pair
     itself.  wk_ctc_forward_train_dropout's rule, raised before any device
@@ -448,8 +537,14 @@ class CTCModel:
         seqs = [tok[b, :ln[b]].tolist() for b in range(tok.shape[0])]
         return (seqs, lp) if return_log_probs else seqs
 
-    def transcribe(self, audio, n_samples: int = MAX_AUDIO_SAMPLES) -> List[List[int]]:
-        """audio -> token id lists (extract_features + model + decode_predictions)."""
+    def transcribe(self, audio, n_samples: int = MAX_AUDIO_SAMPLES, beam: Optional[int] = None) -> List[List[int]]:
+        """audio -> token id lists (extract_features + model + decode_predictions);
+        with beam=W the best hypothesis of beam_decode_audio instead of the
+        greedy path."""
+        if beam is not None:
+            res = self.beam_decode_audio(audio, n_samples, beam=beam)
+            tok, ln = res.tokens.cpu().numpy()[:, 0], res.lengths.cpu().numpy()[:, 0]
+            return [tok[b, :max(ln[b], 0)].tolist() for b in range(tok.shape[0])]
         tok, ln = self.decode_audio(audio, n_samples)
         tok, ln = tok.cpu().numpy(), ln.cpu().numpy()
         return [tok[b, :ln[b]].tolist() for b in range(tok.shape[0])]
@@ -480,6 +575,18 @@ class CTCModel:
         """audio -> Alignment: features(), then align() over all T = 1 +
         n_samples // 160 frames; span_seconds gives the labels' times."""
         return self.align(self.features(audio, n_samples), targets, target_lengths)
+
+    def beam_decode(self, feats, beam: int = 16, top_k: int = 16, n_best: int = 1) -> BeamResult:
+        """Prefix beam search over all T frames: decode(feats,
+        return_log_probs=True), then ctc_beam_search on the (B, T, V)
+        log-probs (fp32 in an fp16 model too)."""
+        _, _, lp = self.decode(feats, return_log_probs=True)
+        return ctc_beam_search(lp, None, beam=beam, top_k=top_k, n_best=n_best, batch_first=True)
+
+    def beam_decode_audio(self, audio, n_samples: int = MAX_AUDIO_SAMPLES, beam: int = 16, top_k: int = 16,
+                          n_best: int = 1) -> BeamResult:
+        """audio -> BeamResult: features(), then beam_decode()."""
+        return self.beam_decode(self.features(audio, n_samples), beam=beam, top_k=top_k, n_best=n_best)
 
     # ---- parameter gradients (fp32 models; wk_ctc_forward_train / wk_ctc_backward) ----
     def forward_train(self, feats, dropout=None, seed: int = 0, offset: int = 0):
@@ -672,6 +779,7 @@ class CTCModel:
         return decode_predictions(log_probs, self._char_map(idx_to_char))
 
     def transcribe_text(self, audio, n_samples: int = MAX_AUDIO_SAMPLES,
-                        idx_to_char: Optional[Mapping[int, str]] = None) -> List[str]:
-        """audio -> text: the device greedy decode, then the idx_to_char map."""
-        return tokens_to_text(self.transcribe(audio, n_samples), self._char_map(idx_to_char))
+                        idx_to_char: Optional[Mapping[int, str]] = None, beam: Optional[int] = None) -> List[str]:
+        """audio -> text: the device greedy decode (beam=W: the beam's best
+        hypothesis), then the idx_to_char map."""
+        return tokens_to_text(self.transcribe(audio, n_samples, beam=beam), self._char_map(idx_to_char))

@@ -515,6 +515,54 @@ wk_status wk_ctc_align(const float* d_log_probs, int64_t batch, int32_t T, int32
                        float* d_frame_lp_or_null, int32_t* d_spans_or_null, float* d_score,
                        int32_t device, void* stream);
 
+/* ---- CTC prefix beam search: the N best label sequences with their log-probabilities
+ * d_log_probs [batch][T][vocab] fp32, blank = 0; beam width W = beam, per-frame
+ * candidate count K = top_k; Tb is d_input_lengths_or_null[b] clamped to [0, T]
+ * (null: all T).  A hypothesis is a label prefix l with two log-masses, pb for
+ * the paths ending in blank and pnb for those ending in its last label e; its
+ * total is p = lse(pb, pnb).  Start: the single hypothesis (), pb = 0, pnb =
+ * -inf.  For each frame t < Tb, with row lp = log_probs[b, t, :]:
+ *   candidates  C_t is the min(K, V-1) non-blank ids with the largest lp, ties to
+ *               the lower id; compares only, so C_t is defined bit for bit.
+ *   stay        every live (l, pb, pnb) in slot order contributes to l:
+ *               pb' (+)= lp[0] + p, and if l is non-empty pnb' (+)= lp[e] + pnb
+ *               (lp[e] is read from the row whether or not e is in C_t).
+ *   extend      every live hypothesis in slot order, for c in C_t in ascending
+ *               id, contributes to l + c: pnb' (+)= lp[c] + (pb if c == e else p).
+ *   merge       (+) is log-add-exp; contributions to the same prefix merge.  The
+ *               only possible merge is an extension (l_i, c) with the stay of a
+ *               live l_j = l_i + c; identity is by prefix, exactly (never by a
+ *               hash alone).
+ *   prune       candidates whose total is -inf are dropped; the W largest
+ *               totals survive, in descending order; equal totals keep
+ *               candidate order (stays in slot order, then extensions by parent
+ *               slot, then token id): a replacement must be strictly greater.
+ * After frame Tb-1 the live hypotheses, in that order, are the result; for
+ * i < n_best:
+ *   d_tokens [batch][n_best][max_len]   the labels, -1 beyond the length
+ *   d_lengths [batch][n_best]           the full length, even beyond max_len (the
+ *                                       tokens are then the first max_len); -1 for a
+ *                                       slot without a hypothesis
+ *   d_scores [batch][n_best]            p, the total; -inf for an empty slot
+ *   d_cand_or_null [batch][T][top_k]    C_t in selection order (descending lp);
+ *                                       -1 at t >= Tb and beyond V-1 entries
+ * Tb = 0 gives the single hypothesis () with score 0.  On NaN input the outputs
+ * are unspecified, but nothing is read or written out of bounds and every
+ * token stays in [-1, vocab).  Arithmetic is fp32, (+) with the device's exp and
+ * log; every sum has one fixed order, so equal inputs give equal bits.
+ * Limits: 1 <= beam <= 64, 1 <= top_k <= 32, 1 <= n_best <= beam, 2 <= vocab <=
+ * 65536, batch * T <= 2^28, max_len >= 1.  Beyond them, or for a null required
+ * pointer, a non-positive size or a workspace not 16-byte aligned:
+ * WK_ERR_INVALID_ARG before any device work; wk_ctc_beam_workspace_bytes
+ * returns 0.  Stream-ordered, no host synchronisation, no atomics; d_workspace
+ * is the caller's. */
+int64_t wk_ctc_beam_workspace_bytes(int64_t batch, int32_t T, int32_t beam, int32_t top_k);
+wk_status wk_ctc_beam(const float* d_log_probs, int64_t batch, int32_t T, int32_t vocab,
+                      const int32_t* d_input_lengths_or_null,
+                      int32_t beam, int32_t top_k, int32_t n_best, int32_t max_len,
+                      void* d_workspace, int32_t* d_tokens, int32_t* d_lengths, float* d_scores,
+                      int32_t* d_cand_or_null, int32_t device, void* stream);
+
 /* ---- WAV ingest and waveform augmentation (host only) ---
  * No device work: these fill caller (e.g. pinned) host buffers for the H2D copy. */
 typedef struct {
