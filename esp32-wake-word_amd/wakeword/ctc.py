@@ -14,6 +14,8 @@ inference surface on the HIP path (wk_ctc_* in the C ABI).
     res = wakeword.ctc_beam_search(log_probs, beam=16, top_k=16, n_best=4)        # prefix beam search: BeamResult(tokens, lengths, scores)
     res = model.beam_decode(feats, beam=16); model.beam_decode_audio(audio, beam=16); beam_texts(res, idx_to_char)
     tokens = model.transcribe(audio, beam=16)            # the best hypothesis of the beam instead of the greedy path
+    sp = wakeword.ctc_spot(log_probs, keywords, keyword_lengths)                  # keyword spotting: Spot(scores, spans, frame_scores)
+    sp = model.spot(feats, keywords); model.spot_audio(audio, keywords); KeywordSpotter(model, char_to_idx, words).detect(audio)
     loss, grads, norm = model.loss_and_grad(feats, targets, input_lengths, target_lengths)   # ctc.py:393-401, fp32
     lp = model.forward_train(feats); flat = model.backward(dlogits); grads = unpack_grads(flat, V)   # its pieces
     model.adam_step(grads, norm)                         # clip_grad_norm_(5.0) + Adam(lr=1e-3) in place, ctc.py:401-402
@@ -433,6 +435,159 @@ def beam_texts(result: BeamResult, idx_to_char: Mapping[int, str]) -> List[List[
                            idx_to_char) for b in range(tok.shape[0])]
 
 
+MAX_KEYWORD_LEN = 32            # wk_ctc_spot: 2S-1 states, one lane each
+
+
+class Spot(NamedTuple):
+    """ctc_spot's result, device tensors: scores (B, K) float32, the best score
+    of keyword k over all segments of utterance b (-inf without an occurrence;
+    with normalize a log-ratio <= 0 whose exp is the confidence); spans
+    (B, K, 2) int32, that segment's frames [start, end) (-1, -1 without);
+    frame_scores (B, K, T) float32 if asked for, the best score of a segment
+    ending at each frame (-inf past the input length), else None."""
+    scores: object
+    spans: object
+    frame_scores: object = None
+
+
+class Detection(NamedTuple):
+    """One keyword found by KeywordSpotter.detect: the utterance's index in the
+    batch, the keyword as given, exp(score) and the span in seconds."""
+    utterance: int
+    keyword: str
+    confidence: float
+    start_s: float
+    end_s: float
+
+
+def keyword_tokens(words: Sequence[str], char_to_idx: Mapping[str, int]) -> Tuple[np.ndarray, np.ndarray]:
+    """Words -> (padded (K, S_max) int32 array, (K,) int32 lengths), one label
+    per character.  KeyError for a character the map does not hold, ValueError
+    for an empty word or one longer than 32."""
+    if isinstance(words, str):
+        words = [words]
+    rows = []
+    for w in words:
+        if not 1 <= len(w) <= MAX_KEYWORD_LEN:
+            raise ValueError(f"keyword {w!r}: length must be in [1, {MAX_KEYWORD_LEN}]")
+        rows.append([int(char_to_idx[c]) for c in w])
+    if not rows:
+        raise ValueError("no keywords")
+    out = np.zeros((len(rows), max(len(r) for r in rows)), dtype=np.int32)
+    for k, r in enumerate(rows):
+        out[k, :len(r)] = r
+    return out, np.array([len(r) for r in rows], dtype=np.int32)
+
+
+def _spot_args(log_probs, keywords, keyword_lengths, input_lengths, batch_first: bool):
+    """ctc_spot's arguments -> (lp (B, T, V), keywords (K, stride) int32,
+    lengths (K,) int32, in_len or None, max_keyword_len), what wk_ctc_spot
+    reads, on log_probs' device; ValueError for what the kernels do not take."""
+    import torch
+    lp = (log_probs if batch_first else log_probs.transpose(0, 1)).detach().contiguous()
+    B, T, V = lp.shape
+    if B < 1 or T < 1 or V < 2:
+        raise ValueError(f"log_probs (B, T, V) = {(B, T, V)}: B and T must be positive and V at least 2")
+    if isinstance(keywords, (list, tuple)) and keywords and isinstance(keywords[0], (list, tuple)):     # a list of int lists
+        if keyword_lengths is None:
+            keyword_lengths = [len(w) for w in keywords]
+        width = max(max(len(w) for w in keywords), 1)
+        keywords = [list(w) + [0] * (width - len(w)) for w in keywords]
+    kw = torch.as_tensor(np.asarray(keywords) if not torch.is_tensor(keywords) else keywords)
+    if kw.dim() != 2 or kw.shape[0] < 1 or kw.shape[1] < 1:
+        raise ValueError(f"keywords must be a non-empty (K, S) array or a list of label lists, got {tuple(kw.shape)}")
+    kw = kw.to(device=lp.device, dtype=torch.int32).contiguous()
+    K = kw.shape[0]
+    if keyword_lengths is None:
+        keyword_lengths = [kw.shape[1]] * K
+    kl = torch.as_tensor(keyword_lengths).reshape(-1).to(device=lp.device, dtype=torch.int32).contiguous()
+    if kl.numel() != K:
+        raise ValueError(f"{K} keywords: {kl.numel()} keyword lengths")
+    max_len = kw.shape[1]
+    if max_len > MAX_KEYWORD_LEN:          # padding wider than the kernel's limit: the longest keyword decides (a host sync)
+        max_len = max(int(kl.max()), 1)
+        if max_len > MAX_KEYWORD_LEN:
+            raise ValueError(f"a keyword of {max_len} labels: at most {MAX_KEYWORD_LEN}")
+    in_len = None
+    if input_lengths is not None:
+        in_len = torch.as_tensor(input_lengths).reshape(-1).to(device=lp.device, dtype=torch.int32).contiguous()
+        if in_len.numel() != B:
+            raise ValueError(f"batch of {B}: {in_len.numel()} input lengths")
+    return lp, kw, kl, in_len, max_len
+
+
+def ctc_spot(log_probs, keywords, keyword_lengths=None, input_lengths=None, normalize: bool = True,
+             frame_scores: bool = False, batch_first: bool = False) -> Spot:
+    """CTC keyword spotting on the HIP device (wk_ctc_spot): for every
+    (utterance, keyword) pair the best score of the keyword's label sequence
+    over all segments of the utterance, and that segment.  log_probs (T, B, V)
+    float32, or (B, T, V) with batch_first=True (used without a copy);
+    keywords a padded (K, S) tensor or array with keyword_lengths (all S when
+    None), or a list of label lists; input_lengths as a tensor or sequence,
+    all T when None.  With normalize (the default) each frame's log-probs are
+    taken relative to the frame's maximum, so the score is <= 0, exactly 0
+    where the greedy path spells the keyword, and exp(score) is a confidence
+    in (0, 1]; without it the score is the segment's path log-probability.
+    frame_scores=True also returns the (B, K, T) per-frame trace.  Runs on the
+    current stream, no host sync; the result is defined bit for bit by the
+    recurrence and tie rule in include/wakeword.h.  span_seconds converts the
+    spans to time."""
+    import torch
+    if not (torch.is_tensor(log_probs) and log_probs.is_cuda and log_probs.dtype == torch.float32 and log_probs.dim() == 3):
+        raise ValueError("log_probs must be a 3-D float32 tensor on the HIP device")
+    lp, kw, kl, in_len, max_len = _spot_args(log_probs, keywords, keyword_lengths, input_lengths, batch_first)
+    B, T, V = lp.shape
+    K = kw.shape[0]
+    L = lib()
+    nbytes = L.wk_ctc_spot_workspace_bytes(B, T, K, max_len)
+    if nbytes <= 0:
+        raise _lib.WakewordError(f"wk_ctc_spot: unsupported shape (B={B}, T={T}, {K} keywords, max keyword length {max_len})")
+    dev = lp.device
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)      # (the caching allocator's: no device malloc per call)
+    scores = torch.empty((B, K), dtype=torch.float32, device=dev)
+    spans = torch.empty((B, K, 2), dtype=torch.int32, device=dev)
+    trace = torch.empty((B, K, T), dtype=torch.float32, device=dev) if frame_scores else None
+
+    def ptr(t):
+        return C.c_void_p(t.data_ptr()) if t is not None else None
+    check(L.wk_ctc_spot(ptr(lp), B, T, V, ptr(in_len), ptr(kw), kw.shape[1], ptr(kl), K, max_len, 1 if normalize else 0, ptr(ws),
+                        ptr(scores), ptr(spans), ptr(trace), dev.index, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+          "wk_ctc_spot")
+    return Spot(scores, spans, trace)
+
+
+class KeywordSpotter:
+    """The reference's CTCKeywordDetector surface (ml_models/test.py:159-235)
+    with a real confidence: where the reference greedy-decodes, tests for a
+    substring and reports a constant 0.9, detect() scores every keyword over
+    every segment of every utterance with CTCModel.spot_audio and reports
+    exp(score) -- 1.0 where the greedy path spells the keyword, less where a
+    competitor wins some frames -- with the segment's time.
+
+        spotter = KeywordSpotter(model, char_to_idx, ["xiao", "a"], threshold=0.8)
+        for d in spotter.detect(audio): d.utterance, d.keyword, d.confidence, d.start_s, d.end_s
+    """
+
+    def __init__(self, model, char_to_idx: Mapping[str, int], keywords: Sequence[str], threshold: float = 0.8,
+                 hop: int = 160, sample_rate: int = 16000):
+        self.model, self.keywords = model, [keywords] if isinstance(keywords, str) else list(keywords)
+        self.tokens, self.lengths = keyword_tokens(self.keywords, char_to_idx)
+        if not 0.0 <= threshold < 1.0:
+            raise ValueError(f"threshold must be in [0, 1), got {threshold!r}")
+        self.threshold, self.hop, self.sample_rate = float(threshold), hop, sample_rate
+
+    def detections(self, spot: Spot) -> List[Detection]:
+        """A Spot of this spotter's keywords -> the pairs with exp(score) >
+        threshold, by utterance, then keyword."""
+        conf = np.exp(spot.scores.cpu().numpy().astype(np.float64))
+        sec = span_seconds(spot.spans.cpu().numpy(), self.hop, self.sample_rate)
+        return [Detection(b, self.keywords[k], float(conf[b, k]), float(sec[b, k, 0]), float(sec[b, k, 1]))
+                for b in range(conf.shape[0]) for k in range(conf.shape[1]) if conf[b, k] > self.threshold]
+
+    def detect(self, audio, n_samples: int = MAX_AUDIO_SAMPLES) -> List[Detection]:
+        return self.detections(self.model.spot_audio(audio, self.tokens, self.lengths, n_samples=n_samples))
+
+
 def dropout_pair(dropout) -> Tuple[float, float]:
     """`dropout` as (p_enc, p_gru): None is (0, 0), a float both sites, a pair
     itself.  wk_ctc_forward_train_dropout's rule, raised before any device
@@ -587,6 +742,21 @@ class CTCModel:
                           n_best: int = 1) -> BeamResult:
         """audio -> BeamResult: features(), then beam_decode()."""
         return self.beam_decode(self.features(audio, n_samples), beam=beam, top_k=top_k, n_best=n_best)
+
+    def spot(self, feats, keywords, keyword_lengths=None, input_lengths=None, normalize: bool = True,
+             frame_scores: bool = False) -> Spot:
+        """Keyword spotting: decode(feats, return_log_probs=True), then
+        ctc_spot on the (B, T, V) log-probs (fp32 in an fp16 model too)."""
+        _, _, lp = self.decode(feats, return_log_probs=True)
+        return ctc_spot(lp, keywords, keyword_lengths, input_lengths, normalize=normalize, frame_scores=frame_scores,
+                        batch_first=True)
+
+    def spot_audio(self, audio, keywords, keyword_lengths=None, n_samples: int = MAX_AUDIO_SAMPLES, normalize: bool = True,
+                   frame_scores: bool = False) -> Spot:
+        """audio -> Spot: features(), then spot() over all T = 1 + n_samples
+        // 160 frames; span_seconds gives the keywords' times."""
+        return self.spot(self.features(audio, n_samples), keywords, keyword_lengths, normalize=normalize,
+                         frame_scores=frame_scores)
 
     # ---- parameter gradients (fp32 models; wk_ctc_forward_train / wk_ctc_backward) ----
     def forward_train(self, feats, dropout=None, seed: int = 0, offset: int = 0):

@@ -563,6 +563,61 @@ wk_status wk_ctc_beam(const float* d_log_probs, int64_t batch, int32_t T, int32_
                       void* d_workspace, int32_t* d_tokens, int32_t* d_lengths, float* d_scores,
                       int32_t* d_cand_or_null, int32_t device, void* stream);
 
+/* ---- CTC keyword spotting: is this word somewhere in the utterance, where, how sure
+ * d_log_probs [batch][T][vocab] fp32, blank = 0; Tb is d_input_lengths_or_null[b]
+ * clamped to [0, T] (null: all T).  Keyword k is d_keywords[k * keyword_stride
+ * + 0..S-1] with S = d_keyword_lengths[k] clamped to [0, max_keyword_len]: labels
+ * w_0..w_{S-1}, 1 <= S <= 32, each in [1, vocab).  Every (utterance, keyword)
+ * pair is scored.  The keyword's lattice has L = 2S-1 states: even state j
+ * emits w_{j/2}, odd state j emits blank; there are no outer blanks, so a span
+ * is tight.  With g_t = max_v lp_t(v) when normalize != 0 (else g_t is not used):
+ *   x_t(j) = lp_t(l_j)                                       normalize == 0 (the input's bits)
+ *   x_t(j) = lp_t(l_j) == -inf ? -inf : lp_t(l_j) - g_t      normalize != 0 (one IEEE subtract)
+ *   a_{-1}(j) = -inf
+ *   a_t(0) = x_t(0) + max(a_{t-1}(0), 0)                     0: the keyword may start at any frame
+ *   a_t(j) = x_t(j) + max(a_{t-1}(j), a_{t-1}(j-1), [a_{t-1}(j-2)])
+ *                                 third term: j even, j >= 2, w_{j/2} != w_{j/2-1}
+ *   e_t    = a_t(L-1)
+ *   score  = max_{t < Tb} e_t
+ * Every state carries the frame at which its best path entered state 0: an
+ * entry at frame t carries t, any other move the chosen predecessor's value, a
+ * state whose value is -inf carries -1.  Tie rule: a candidate replaces the
+ * best so far only if strictly greater; candidates are tried in the order
+ * stay, j-1, j-2 (at state 0: stay, then enter).  Over t the first frame that
+ * attains the maximum wins, and span = [start carried by state L-1 at that
+ * frame, that frame + 1).  max is exact and every add or subtract rounds once
+ * in fp32, so every output is defined bit for bit by the recurrence, whatever
+ * the lane layout.  With normalize every x <= 0 and the score is the best
+ * log-ratio, over all segments, between the keyword's best path and the greedy
+ * path on the same frames: 0 exactly where the greedy path spells the keyword,
+ * and exp(score) is a confidence in (0, 1].
+ * Outputs:
+ *   d_scores [batch][n_keywords]                  the score
+ *   d_spans [batch][n_keywords][2]                the span, frames [start, end)
+ *   d_frame_scores_or_null [batch][n_keywords][T] e_t, -inf at t >= Tb: the trace a
+ *                                                 streaming detector thresholds, and
+ *                                                 from which further occurrences are read
+ * No occurrence -- Tb < S + the number of adjacent equal labels, Tb = 0, a
+ * keyword of length <= 0, a keyword with a label outside [1, vocab) (never used
+ * as an index), or every path through a -inf -- gives score -inf and span
+ * (-1, -1) (and a trace of -inf for an empty or invalid keyword); the other
+ * pairs are unaffected.  On NaN input the outputs are unspecified, but every
+ * span value stays in [-1, T].
+ * Limits: 1 <= max_keyword_len <= 32, vocab <= 65536, batch * T <= 2^28, 1 <=
+ * n_keywords, batch * n_keywords <= 2^24, keyword_stride >= max_keyword_len.
+ * Beyond them, or for a null required pointer, a non-positive size, a workspace
+ * not 16-byte aligned or device < 0: WK_ERR_INVALID_ARG before any device work;
+ * wk_ctc_spot_workspace_bytes returns 0 beyond the limits.  The workspace holds
+ * g [batch][T] and nothing per pair.  Stream-ordered, no host synchronisation,
+ * no atomics (equal inputs give equal bits); d_workspace is the caller's. */
+int64_t wk_ctc_spot_workspace_bytes(int64_t batch, int32_t T, int32_t n_keywords, int32_t max_keyword_len);
+wk_status wk_ctc_spot(const float* d_log_probs, int64_t batch, int32_t T, int32_t vocab,
+                      const int32_t* d_input_lengths_or_null,
+                      const int32_t* d_keywords, int32_t keyword_stride, const int32_t* d_keyword_lengths,
+                      int32_t n_keywords, int32_t max_keyword_len, int32_t normalize,
+                      void* d_workspace, float* d_scores, int32_t* d_spans, float* d_frame_scores_or_null,
+                      int32_t device, void* stream);
+
 /* ---- WAV ingest and waveform augmentation (host only) ---
  * No device work: these fill caller (e.g. pinned) host buffers for the H2D copy. */
 typedef struct {
