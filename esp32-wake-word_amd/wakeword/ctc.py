@@ -16,6 +16,8 @@ inference surface on the HIP path (wk_ctc_* in the C ABI).
     tokens = model.transcribe(audio, beam=16)            # the best hypothesis of the beam instead of the greedy path
     sp = wakeword.ctc_spot(log_probs, keywords, keyword_lengths)                  # keyword spotting: Spot(scores, spans, frame_scores)
     sp = model.spot(feats, keywords); model.spot_audio(audio, keywords); KeywordSpotter(model, char_to_idx, words).detect(audio)
+    st = wakeword.edit_distance(tokens, lengths, targets, target_lengths)         # EditStats(distance, substitutions, deletions, ...)
+    st = model.cer(feats, targets, target_lengths, beam=16, n_best=4); error_rate(st); error_rate(st, oracle=True)
     loss, grads, norm = model.loss_and_grad(feats, targets, input_lengths, target_lengths)   # ctc.py:393-401, fp32
     lp = model.forward_train(feats); flat = model.backward(dlogits); grads = unpack_grads(flat, V)   # its pieces
     model.adam_step(grads, norm)                         # clip_grad_norm_(5.0) + Adam(lr=1e-3) in place, ctc.py:401-402
@@ -588,6 +590,140 @@ class KeywordSpotter:
         return self.detections(self.model.spot_audio(audio, self.tokens, self.lengths, n_samples=n_samples))
 
 
+MAX_REF_LEN = 1024              # wk_ctc_cer: 64 lanes x 16 reference columns
+MAX_HYP_STRIDE = 32767          # ... d <= 32767 keeps d * 2^16 + s a positive int32
+MAX_N_HYP = 64
+
+
+class EditStats(NamedTuple):
+    """edit_distance's result, device tensors.  distance, substitutions,
+    deletions, insertions: int32, (B, n_hyp) -- (B,) for a 2-D hyp -- the
+    Levenshtein distance d of each hypothesis to its utterance's reference, the
+    fewest substitutions s among the alignments that reach d, and the del and
+    ins that d = s + del + ins and ins - del = N - M then fix.  best (B,) int32:
+    the hypothesis with the smallest (d, s, index), the oracle of an N-best
+    list.  totals (2, 8) int64: row 0 over hypothesis 0 of every utterance, row
+    1 over the oracle; columns sum d, sum s, sum del, sum ins, sum M (reference
+    tokens), sum N (hypothesis tokens), utterances with d > 0, B."""
+    distance: object
+    substitutions: object
+    deletions: object
+    insertions: object
+    best: object
+    totals: object
+
+    def error_rate(self, oracle: bool = False) -> float:
+        return error_rate(self.totals, oracle)
+
+    def sentence_error_rate(self, oracle: bool = False) -> float:
+        """The share of utterances with d > 0 (one read-back)."""
+        row = self.totals[1 if oracle else 0].tolist()
+        return row[6] / row[7]
+
+
+def _rate(errors: int, tokens: int) -> float:
+    if tokens == 0:
+        return float("nan") if errors == 0 else float("inf")
+    return errors / tokens
+
+
+def error_rate(totals, oracle: bool = False) -> float:
+    """The corpus error rate sum d / sum M of a totals block ((2, 8), row 1 with
+    oracle=True) or of one row ((8,), e.g. a sum of CTCTrainer.val_cer rows), as
+    a float: one read-back.  nan when there are no reference tokens and no
+    errors, inf when there are none but errors."""
+    t = totals.totals if isinstance(totals, EditStats) else totals
+    t = t.tolist() if hasattr(t, "tolist") else list(t)
+    if t and isinstance(t[0], (list, tuple)):
+        t = t[1 if oracle else 0]
+    elif oracle:
+        raise ValueError("oracle=True needs the (2, 8) totals, got one row")
+    if len(t) != 8:
+        raise ValueError(f"totals must be (2, 8) or (8,), got a row of {len(t)}")
+    return _rate(int(t[0]), int(t[4]))
+
+
+def _cer_args(hyp, hyp_lengths, ref, ref_lengths, collapse: bool):
+    """edit_distance's arguments -> (hyp (B, n_hyp, stride) int32, hyp_len
+    (B * n_hyp,) int32 or None, ref (B, ref_stride) int32, ref_len (B,) int32,
+    max_ref_len), what wk_ctc_cer reads, on hyp's device; ValueError for what
+    the kernel does not take."""
+    import torch
+    if not (torch.is_tensor(hyp) and hyp.dtype == torch.int32 and hyp.dim() in (2, 3)):
+        raise ValueError("hyp must be a (B, N) or (B, n_hyp, N) int32 tensor")
+    h = hyp.detach().unsqueeze(1) if hyp.dim() == 2 else hyp.detach()
+    B, H, stride = h.shape
+    if B < 1 or H < 1 or stride < 1:
+        raise ValueError(f"hyp (B, n_hyp, N) = {(B, H, stride)}: every size must be positive")
+    if H > MAX_N_HYP:
+        raise ValueError(f"{H} hypotheses per utterance: at most {MAX_N_HYP}")
+    if stride > MAX_HYP_STRIDE:
+        raise ValueError(f"hypothesis rows of {stride}: at most {MAX_HYP_STRIDE}")
+    if B * H > 2 ** 24 or B * H * stride > 2 ** 30:
+        raise ValueError(f"hyp (B, n_hyp, N) = {(B, H, stride)}: B * n_hyp must be at most 2^24 and B * n_hyp * N at most 2^30")
+    h = h.contiguous()
+    hl = None
+    if hyp_lengths is not None:
+        hl = torch.as_tensor(hyp_lengths).reshape(-1).to(device=h.device, dtype=torch.int32).contiguous()
+        if hl.numel() != B * H:
+            raise ValueError(f"{B} x {H} hypotheses: {hl.numel()} hypothesis lengths")
+    elif not collapse:
+        raise ValueError("hyp_lengths is required unless collapse is set")
+    r = torch.as_tensor(np.asarray(ref) if not torch.is_tensor(ref) else ref)
+    if r.dim() != 2 or r.is_floating_point():
+        raise ValueError(f"ref must be a (B, S) integer array, got {tuple(r.shape)} {r.dtype}")
+    if r.shape[1] == 0:
+        r = torch.zeros((r.shape[0], 1), dtype=torch.int32, device=r.device)
+    r = r.to(device=h.device, dtype=torch.int32).contiguous()
+    rl = torch.as_tensor(ref_lengths).reshape(-1).to(device=h.device, dtype=torch.int32).contiguous()
+    if r.shape[0] != B or rl.numel() != B:
+        raise ValueError(f"batch of {B}: ref {tuple(r.shape)}, {rl.numel()} reference lengths")
+    max_ref_len = r.shape[1]
+    if max_ref_len > MAX_REF_LEN:          # padding wider than the kernel's limit: the longest reference decides (a host sync)
+        max_ref_len = max(int(rl.max()), 1)
+        if max_ref_len > MAX_REF_LEN:
+            raise ValueError(f"a reference of {max_ref_len} tokens: at most {MAX_REF_LEN}")
+    return h, hl, r, rl, max_ref_len
+
+
+def edit_distance(hyp, hyp_lengths, ref, ref_lengths, collapse: bool = False) -> EditStats:
+    """Edit distance of hypotheses to references on the HIP device
+    (wk_ctc_cer), with its split into substitutions, deletions and insertions,
+    the oracle hypothesis per utterance and the corpus totals (error_rate turns
+    them into a rate).  hyp: a (B, N) or (B, n_hyp, N) int32 device tensor,
+    hypothesis h of utterance b against reference b -- CTCModel.decode's tokens
+    and lengths, or ctc_beam_search's (a slot's -1 length is an empty
+    hypothesis).  With collapse=True hyp holds per-frame labels
+    (CTCModel.frame_argmax), the hypothesis is their greedy CTC collapse and
+    hyp_lengths the frames per row, all N when None.  ref (B, S) padded, as a
+    tensor or array, with ref_lengths.  Tokens are only compared for equality.
+    Runs on the current stream, no host sync; every output is integer, defined
+    bit for bit in include/wakeword.h."""
+    import torch
+    if not (torch.is_tensor(hyp) and hyp.is_cuda):
+        raise ValueError("hyp must be an int32 tensor on the HIP device")
+    squeeze = hyp.dim() == 2
+    h, hl, r, rl, max_ref_len = _cer_args(hyp, hyp_lengths, ref, ref_lengths, collapse)
+    B, H, stride = h.shape
+    L = lib()
+    nbytes = L.wk_ctc_cer_workspace_bytes(B, H, stride, max_ref_len)
+    if nbytes <= 0:
+        raise _lib.WakewordError(f"wk_ctc_cer: unsupported shape (B={B}, n_hyp={H}, N={stride}, max reference length {max_ref_len})")
+    dev = h.device
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)      # (the caching allocator's: no device malloc per call)
+    stats = torch.empty((B, H, 4), dtype=torch.int32, device=dev)
+    best = torch.empty((B,), dtype=torch.int32, device=dev)
+    totals = torch.empty((2, 8), dtype=torch.int64, device=dev)
+
+    def ptr(t):
+        return C.c_void_p(t.data_ptr()) if t is not None else None
+    check(L.wk_ctc_cer(ptr(h), ptr(hl), B, H, stride, ptr(r), r.shape[1], ptr(rl), max_ref_len, 1 if collapse else 0, ptr(ws),
+                       ptr(stats), ptr(best), ptr(totals), dev.index, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+          "wk_ctc_cer")
+    cols = [stats[:, 0, k] if squeeze else stats[:, :, k] for k in range(4)]
+    return EditStats(cols[0], cols[1], cols[2], cols[3], best, totals)
+
+
 def dropout_pair(dropout) -> Tuple[float, float]:
     """`dropout` as (p_enc, p_gru): None is (0, 0), a float both sites, a pair
     itself.  wk_ctc_forward_train_dropout's rule, raised before any device
@@ -757,6 +893,31 @@ class CTCModel:
         // 160 frames; span_seconds gives the keywords' times."""
         return self.spot(self.features(audio, n_samples), keywords, keyword_lengths, normalize=normalize,
                          frame_scores=frame_scores)
+
+    def cer(self, feats, targets, target_lengths, beam: Optional[int] = None, top_k: int = 16, n_best: int = 1,
+            input_lengths=None) -> EditStats:
+        """The edit statistics of this model's transcripts against `targets`
+        (ctc_loss's forms), nothing leaving the device.  Greedy (beam=None):
+        decode, frame_argmax, then edit_distance collapsing the per-frame
+        labels.  beam=W: beam_decode's n_best hypotheses, all compared, so
+        EditStats.best and totals[1] are the beam's oracle.  input_lengths:
+        frames per utterance, all T when None.  error_rate(stats) is the CER."""
+        import torch
+        labels = pad_targets(targets, target_lengths)
+        if beam is None:
+            if n_best != 1:
+                raise ValueError(f"n_best={n_best!r} needs a beam: the greedy path has one hypothesis")
+            f = torch.as_tensor(feats, dtype=torch.float32)
+            self.decode(f)
+            return edit_distance(self.frame_argmax(f.shape[0], f.shape[1]), input_lengths, labels, target_lengths, collapse=True)
+        _, _, lp = self.decode(feats, return_log_probs=True)
+        res = ctc_beam_search(lp, input_lengths, beam=beam, top_k=top_k, n_best=n_best, batch_first=True)
+        return edit_distance(res.tokens, res.lengths, labels, target_lengths)
+
+    def cer_audio(self, audio, targets, target_lengths, n_samples: int = MAX_AUDIO_SAMPLES, beam: Optional[int] = None,
+                  top_k: int = 16, n_best: int = 1) -> EditStats:
+        """audio -> EditStats: features(), then cer() over all T = 1 + n_samples // 160 frames."""
+        return self.cer(self.features(audio, n_samples), targets, target_lengths, beam=beam, top_k=top_k, n_best=n_best)
 
     # ---- parameter gradients (fp32 models; wk_ctc_forward_train / wk_ctc_backward) ----
     def forward_train(self, feats, dropout=None, seed: int = 0, offset: int = 0):

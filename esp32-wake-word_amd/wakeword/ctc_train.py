@@ -25,7 +25,7 @@ from typing import Dict, Iterable, Mapping, Optional, Tuple
 
 import numpy as np
 
-from .ctc import CTCModel, _as_f32, dropout_pair, pack_state_dict, unpack_grads
+from .ctc import CTCModel, _as_f32, dropout_pair, error_rate, pack_state_dict, unpack_grads
 
 
 def check_hyper(lr, betas, eps, weight_decay, max_norm) -> None:
@@ -111,6 +111,14 @@ class CTCTrainer:
         """The validation loss of ctc.py:409-425 at the current weights: eval mode, no dropout."""
         return self.model.loss(feats, targets, input_lengths, target_lengths)
 
+    def val_cer(self, feats, targets, input_lengths, target_lengths):
+        """The edit totals of the greedy transcripts at the current weights
+        (CTCModel.cer, the first input_lengths[b] frames of each utterance):
+        EditStats.totals' row 0 as an (8,) int64 device tensor -- sum d, sum s,
+        sum del, sum ins, sum M, sum N, utterances with d > 0, B -- so an epoch
+        adds its batches' rows and reads back once (error_rate of the sum)."""
+        return self.model.cer(feats, targets, target_lengths, input_lengths=input_lengths).totals[0]
+
     def weights(self):
         return self.model.weights()
 
@@ -131,7 +139,7 @@ class CTCTrainer:
 
 
 def train_ctc(train_loader: Iterable, val_loader: Iterable, vocab: int, num_epochs: int = 30, patience: int = 5,
-              trainer=None, weights=None, **hyper):
+              trainer=None, weights=None, history=None, **hyper):
     """THCHS30Trainer.train's loop (ctc.py:374-447) without the download, the
     file save and the plot.  Batches are (features, labels, feature_lengths,
     label_lengths), as collate_fn yields them.  Per epoch: one trainer.step
@@ -143,7 +151,11 @@ def train_ctc(train_loader: Iterable, val_loader: Iterable, vocab: int, num_epoc
     built from `weights` -- default: torch's initialisation at seed 0 -- and
     **hyper when None.  **hyper are CTCTrainer's keywords; among them
     `dropout` (default 0: off; the reference trains at 0.2, ctc.py:34) and the
-    masks' `seed`.  Returns (trainer, train_losses, val_losses, best_state_dict)."""
+    masks' `seed`.  `history`: a dict; the loop then also measures each epoch's
+    corpus character error rate on the validation set (trainer.val_cer per
+    batch, summed on the device, error_rate of the sum) and appends it to
+    history["val_cer"].  Model selection stays on the validation loss either
+    way.  Returns (trainer, train_losses, val_losses, best_state_dict)."""
     if trainer is None:
         if weights is None:
             from .ctc import random_state_dict
@@ -163,6 +175,12 @@ def train_ctc(train_loader: Iterable, val_loader: Iterable, vocab: int, num_epoc
     for _ in range(num_epochs):
         train_losses.append(mean([trainer.step(*batch) for batch in train_loader]))
         val_losses.append(mean([trainer.val_loss(*batch) for batch in val_loader]))
+        if history is not None:
+            totals = None      # (summed on the device: one read-back per epoch)
+            for batch in val_loader:
+                row = trainer.val_cer(*batch)
+                totals = row if totals is None else totals + row
+            history.setdefault("val_cer", []).append(error_rate(totals) if totals is not None else float("nan"))
         if val_losses[-1] < best:
             best, best_sd, stale = val_losses[-1], trainer.state_dict(), 0
         else:

@@ -618,6 +618,56 @@ wk_status wk_ctc_spot(const float* d_log_probs, int64_t batch, int32_t T, int32_
                       void* d_workspace, float* d_scores, int32_t* d_spans, float* d_frame_scores_or_null,
                       int32_t device, void* stream);
 
+/* ---- Edit distance and error rates: how well the decoded hypotheses match the references
+ * d_hyp [batch][n_hyp][hyp_stride] int32 hypotheses, d_ref [batch][ref_stride]
+ * int32 references; pair (b, h) compares hypothesis h of utterance b with
+ * reference b.  M is d_ref_lengths[b] clamped to [0, max_ref_len].  The
+ * hypothesis and its length N depend on `collapse`:
+ *   collapse == 0   the hypothesis is d_hyp[b][h][0..N), N = d_hyp_lengths[b *
+ *                   n_hyp + h] clamped to [0, hyp_stride]: a beam slot's -1
+ *                   becomes 0, a beam length beyond max_len the stored prefix
+ *                   (wk_ctc_forward's d_tokens / d_lengths with n_hyp = 1,
+ *                   wk_ctc_beam's with n_hyp = n_best).  d_hyp_lengths is required.
+ *   collapse != 0   d_hyp[b][h][0..Tb) are per-frame labels (wk_ctc_frame_argmax's
+ *                   output with hyp_stride = T), Tb = d_hyp_lengths[b * n_hyp + h]
+ *                   clamped to [0, hyp_stride], all hyp_stride when the pointer is
+ *                   null.  The hypothesis is the labels of the frames t with
+ *                   label_t != 0 && label_t != label_{t-1} (label_{-1} = 0), the
+ *                   greedy CTC collapse; N is their count.
+ * Tokens are compared as int32 for equality only, never used as an index, and
+ * nothing at or beyond a length is read into a result.
+ * An alignment is a monotone path of three moves: match or substitute (h_i with
+ * r_j), insertion (h_i alone), deletion (r_j alone).  d is the minimum number
+ * of non-match moves, the Levenshtein distance; s the minimum number of
+ * substitutions among the alignments that reach d; ins - del = N - M and d = s +
+ * del + ins fix del and ins.  So the four numbers are properties of the two
+ * sequences, not of a tie rule.  Equivalently d * 2^16 + s is the minimum of one
+ * additive cost: match 0, insertion and deletion 2^16, substitution 2^16 + 1.
+ * Outputs:
+ *   d_stats [batch][n_hyp][4] int32     d, s, del, ins
+ *   d_best_or_null [batch] int32        the h with the smallest (d, s, h): the oracle
+ *                                       hypothesis of the N-best list
+ *   d_totals_or_null [2][8] int64       row 0 over hypothesis 0 of every utterance, row
+ *                                       1 over the oracle hypothesis; columns: sum d,
+ *                                       sum s, sum del, sum ins, sum M, sum N, the number
+ *                                       of utterances with d > 0, batch.  The corpus
+ *                                       error rate is column 0 / column 4.
+ * Everything is integer arithmetic, so equal inputs give equal bits.
+ * Limits: 1 <= hyp_stride <= 32767, 1 <= max_ref_len <= 1024, ref_stride >=
+ * max_ref_len, 1 <= n_hyp <= 64, batch * n_hyp <= 2^24, batch * n_hyp *
+ * hyp_stride <= 2^30.  Beyond them, or for a null required pointer, a
+ * non-positive size, a workspace not 16-byte aligned or device < 0:
+ * WK_ERR_INVALID_ARG before any device work; wk_ctc_cer_workspace_bytes returns
+ * 0 beyond the limits.  The workspace holds (N, M) per pair and nothing
+ * proportional to hyp_stride * max_ref_len: no DP matrix, no back-pointers.
+ * Stream-ordered, no host synchronisation, no atomics, no floating point;
+ * d_workspace is the caller's. */
+int64_t wk_ctc_cer_workspace_bytes(int64_t batch, int32_t n_hyp, int32_t hyp_stride, int32_t max_ref_len);
+wk_status wk_ctc_cer(const int32_t* d_hyp, const int32_t* d_hyp_lengths_or_null, int64_t batch, int32_t n_hyp,
+                     int32_t hyp_stride, const int32_t* d_ref, int32_t ref_stride, const int32_t* d_ref_lengths,
+                     int32_t max_ref_len, int32_t collapse, void* d_workspace, int32_t* d_stats,
+                     int32_t* d_best_or_null, int64_t* d_totals_or_null, int32_t device, void* stream);
+
 /* ---- WAV ingest and waveform augmentation (host only) ---
  * No device work: these fill caller (e.g. pinned) host buffers for the H2D copy. */
 typedef struct {
