@@ -204,6 +204,21 @@ __device__ __forceinline__ float wave_sum(float v) {
   return (r0 + r1) + (r2 + r3);
 }
 
+// Maximum over the 64 lanes, in every lane: wave_sum's butterflies with max.
+// Must be called with all 64 lanes active.
+template <int CTRL> __device__ __forceinline__ float max_dpp(float v) { return fmaxf(v, dpp<CTRL>(v)); }
+__device__ __forceinline__ float wave_max(float v) {
+  v = max_dpp<0xB1>(v);
+  v = max_dpp<0x4E>(v);
+  v = max_dpp<0x141>(v);
+  v = max_dpp<0x140>(v);
+  const float r0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__float_as_int(v), 0));
+  const float r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__float_as_int(v), 16));
+  const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__float_as_int(v), 32));
+  const float r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__float_as_int(v), 48));
+  return fmaxf(fmaxf(r0, r1), fmaxf(r2, r3));
+}
+
 // Buffer-resource loads: base in SGPRs, per-lane byte offset in one VGPR, a
 // wave-uniform byte offset in an SGPR -- no 64-bit VGPR address per load.
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, uint32_t bytes) {

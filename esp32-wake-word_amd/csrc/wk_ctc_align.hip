@@ -14,16 +14,14 @@
 // defined bit for bit by the recurrence, whatever the lane layout.
 //
 // Four launches on the caller's stream, no host synchronisation, no atomics:
-//   prep     one block per utterance: lengths clamped, labels validated and
-//            copied, the spans preset to -1;
-//   gather   lp_t(l'_s) into a dense [B][T][Ls] buffer, parallel over t (-inf at
-//            s >= L), as wk_ctc_loss does;
-//   recur    one wave per utterance: lane i holds the R = Ls/64 states i*R ..
-//            i*R+R-1 in registers, the two neighbour values come from the
-//            previous lane by a DPP wave shift, the gathered rows are loaded a
-//            group of steps ahead.  Per step a lane packs its R two-bit
-//            back-pointers into one word and stores it: one coalesced row of 64
-//            words per (b, t); no alpha row is stored.  The same wave then
+//   prep     one block per utterance: the lattice's inputs (lengths, labels:
+//            wk_ctc_lattice_dev.h), the spans preset to -1;
+//   gather   lp_t(l'_s) into a dense [B][T][Ls] buffer (wk_ctc_lattice_dev.h);
+//   recur    one wave per utterance on the register-row layout of
+//            wk_ctc_lattice_dev.h, the gathered rows loaded a group of steps
+//            ahead.  Per step a lane packs its R two-bit back-pointers into
+//            one word and stores it: one coalesced row of 64 words per (b, t);
+//            no alpha row is stored.  The same wave then
 //            walks the path back: lane i re-loads word i of a group of rows (the
 //            addresses do not depend on the path, so the loads run ahead), and
 //            each step is a v_readlane at the uniform index s / R and scalar
@@ -34,15 +32,11 @@
 #include <math.h>
 
 #include "wakeword.h"
-#include "wk_common.h"
-#include "wk_kernels.h"
+#include "wk_ctc_lattice_dev.h"
 
 namespace wk {
 namespace {
 
-constexpr int kCtcAlignMaxLabels = 255;      // L = 511 states: 8 registers per lane
-constexpr int kCtcAlignMaxVocab = 65536;
-constexpr int64_t kCtcAlignMaxFrames = (int64_t)1 << 28;   // batch * T
 constexpr int kBackChunk = 64;               // frames per backtrace chunk: one back-pointer row per register, one state per lane
 constexpr int kPadRows = 128;                // back-pointer rows of slack between lpg and bp (below)
 
@@ -58,29 +52,18 @@ struct CtcAlignWs {
   int64_t bytes;
 };
 
-// States per row, rounded to 64 R with R in {1, 2, 4, 8}; 0 beyond the limit.
-int ctc_align_row(int max_label_len) {
-  const int L = 2 * max_label_len + 1;
-  for (int r = 1; r <= 8; r *= 2)
-    if (L <= 64 * r) return 64 * r;
-  return 0;
-}
-
 CtcAlignWs ctc_align_layout(void* base, int64_t batch, int32_t T, int32_t max_label_len) {
   CtcAlignWs w;
-  w.ls = ctc_align_row(max_label_len);
+  w.ls = ctc_lattice_row(max_label_len);
   w.smax = max_label_len > 0 ? max_label_len : 1;
   const int64_t frames = batch * T;
   w.lpg = (float*)base;
   w.bp = (uint32_t*)(w.lpg + frames * w.ls) + kPadRows * 64;
   w.meta = (int32_t*)(w.bp + frames * 64);
   w.lab = w.meta + 4 * batch;
-  w.bytes = (int64_t)4 * (frames * w.ls + (frames + kPadRows) * 64 + 4 * batch + batch * w.smax);
-  w.bytes = (w.bytes + 255) & ~(int64_t)255;
+  w.bytes = round_up_256((int64_t)4 * (frames * w.ls + (frames + kPadRows) * 64 + 4 * batch + batch * w.smax));
   return w;
 }
-
-__device__ __forceinline__ float neg_inf() { return -__builtin_inff(); }
 
 // ---- prep -------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void ctc_align_prep_kernel(const int32_t* __restrict__ labels, int label_stride,
@@ -88,87 +71,28 @@ __global__ __launch_bounds__(256) void ctc_align_prep_kernel(const int32_t* __re
                                                              const int32_t* __restrict__ lab_len, int T, int V, int max_label_len,
                                                              int32_t* __restrict__ spans, CtcAlignWs w) {
   const int b = blockIdx.x, i = threadIdx.x;
-  const int Tb = min(max(in_len[b], 0), T);
-  const int S = min(max(lab_len[b], 0), max_label_len);
-  int bad = 0;
-  if (i < S) {
-    int v = labels[(int64_t)b * label_stride + i];
-    bad = v < 1 || v >= V;
-    if (bad) v = 0;                          // never an index; the utterance gets no alignment
-    w.lab[(int64_t)b * w.smax + i] = v;
-  }
+  const LatticePrep p = lattice_prep_labels(labels, label_stride, in_len, lab_len, T, V, max_label_len, w);
   if (spans && i < max_label_len) {          // emit overwrites the labels an alignment places
     spans[((int64_t)b * max_label_len + i) * 2] = -1;
     spans[((int64_t)b * max_label_len + i) * 2 + 1] = -1;
   }
-  const int any_bad = __syncthreads_or(bad);
-  if (i == 0) {
-    w.meta[4 * b + 0] = Tb;
-    w.meta[4 * b + 1] = S;
-    w.meta[4 * b + 2] = !any_bad;
-  }
-}
-
-// ---- gather -----------------------------------------------------------------------
-__global__ __launch_bounds__(256) void ctc_align_gather_kernel(const float* __restrict__ lp, int T, int V, int ls_shift,
-                                                               int64_t total, CtcAlignWs w) {
-  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= total) return;                                        // total = batch * T * ls
-  const int s = (int)(idx & (w.ls - 1));
-  const int64_t bt = idx >> ls_shift;
-  const int b = (int)(bt / T), t = (int)(bt % T);
-  const int Tb = w.meta[4 * b], S = w.meta[4 * b + 1];
-  if (t >= Tb) return;
-  if (s > 2 * S) {                 // past the last state: -inf, which the recursion relies on
-    w.lpg[idx] = neg_inf();
-    return;
-  }
-  const int v = (s & 1) ? w.lab[(int64_t)b * w.smax + (s >> 1)] : 0;
-  w.lpg[idx] = lp[bt * V + v];
+  lattice_prep_meta(p.Tb, p.S, __syncthreads_or(p.bad), w);
 }
 
 // ---- recursion and backtrace ------------------------------------------------------
-template <int R> __device__ __forceinline__ void ld_row(const float* p, float (&r)[R]) {
-  if constexpr (R == 1) {
-    r[0] = p[0];
-  } else if constexpr (R == 2) {
-    const float2 v = *reinterpret_cast<const float2*>(p);
-    r[0] = v.x;
-    r[1] = v.y;
-  } else {
-#pragma unroll
-    for (int k = 0; k < R / 4; ++k) {
-      const float4 v = reinterpret_cast<const float4*>(p)[k];
-      r[4 * k] = v.x, r[4 * k + 1] = v.y, r[4 * k + 2] = v.z, r[4 * k + 3] = v.w;
-    }
-  }
-}
-
-// The value of the previous lane (wave_shr:1); -inf in lane 0.
-__device__ __forceinline__ float from_prev_lane(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(neg_inf()), __float_as_int(v), 0x138, 0xF, 0xF, false));
-}
-
 // One step: a <- x + max(a, the neighbours'), x the gathered row (-inf at s >= L,
 // which keeps those states at -inf).  Returns the lane's back-pointers, two
 // bits per state: how far back (0, 1 or 2 states) the maximum lies.
 template <int R> __device__ __forceinline__ uint32_t ctc_align_step(float (&a)[R], const float (&x)[R], const bool (&skip)[R]) {
-  float n1[R], n2[R];
-  const float p1 = from_prev_lane(a[R - 1]);
-  const float p2 = R >= 2 ? from_prev_lane(a[R >= 2 ? R - 2 : 0]) : from_prev_lane(p1);
-#pragma unroll
-  for (int j = 0; j < R; ++j) {
-    n1[j] = j >= 1 ? a[j >= 1 ? j - 1 : 0] : p1;
-    n2[j] = j >= 2 ? a[j >= 2 ? j - 2 : 0] : (j == 1 ? p1 : p2);
-  }
+  const LatticeNb<R> n = lattice_neighbours<R, false>(a);
   uint32_t word = 0;
 #pragma unroll
   for (int j = 0; j < R; ++j) {
     float best = a[j];
     uint32_t k = 0;
-    if (n1[j] > best) best = n1[j], k = 1;
+    if (n.n1[j] > best) best = n.n1[j], k = 1;
     if (!(R % 2 == 0 && j % 2 == 0)) {      // (an even state is a blank: two terms)
-      if (skip[j] && n2[j] > best) best = n2[j], k = 2;
+      if (skip[j] && n.n2[j] > best) best = n.n2[j], k = 2;
     }
     a[j] = x[j] + best;
     word |= k << (2 * j);
@@ -278,7 +202,7 @@ __global__ __launch_bounds__(64) void ctc_align_recur_kernel(int T, CtcAlignWs w
 #pragma unroll
       for (int k = 0; k < G; ++k) {
         mine = lane == k ? s : mine;
-        const uint32_t word = (uint32_t)__builtin_amdgcn_readlane((int)row[k], s >> LOG_R);
+        const uint32_t word = read_lane(row[k], s >> LOG_R);
         row[k] = src[-(int64_t)k * 64];
         const int back = (int)((word >> (2 * (s & (R - 1)))) & 3u);
         s -= min(back, s);
@@ -318,21 +242,15 @@ __global__ __launch_bounds__(256) void ctc_align_emit_kernel(const int32_t* __re
   }
 }
 
-template <int R> void launch_recur(int64_t batch, int T, const CtcAlignWs& w, int32_t* states, float* score, hipStream_t st) {
-  hipLaunchKernelGGL(ctc_align_recur_kernel<R>, dim3((unsigned)batch), dim3(64), 0, st, T, w, states, score);
-}
-
 }  // namespace
 }  // namespace wk
 
-using wk::hip_fail;
 using wk::invalid;
 
 extern "C" {
 
 int64_t wk_ctc_align_workspace_bytes(int64_t batch, int32_t T, int32_t max_label_len) {
-  if (batch <= 0 || T <= 0 || max_label_len < 0 || max_label_len > wk::kCtcAlignMaxLabels || batch * T > wk::kCtcAlignMaxFrames)
-    return 0;
+  if (!wk::ctc_lattice_shape_ok(batch, T, max_label_len)) return 0;
   return wk::ctc_align_layout(nullptr, batch, T, max_label_len).bytes;
 }
 
@@ -344,9 +262,9 @@ wk_status wk_ctc_align(const float* d_log_probs, int64_t batch, int32_t T, int32
     return invalid("wk_ctc_align: null pointer");
   if (batch <= 0 || T <= 0 || vocab <= 0) return invalid("wk_ctc_align: batch, T and vocab must be positive");
   if (max_label_len < 0 || label_stride < max_label_len) return invalid("wk_ctc_align: label_stride < max_label_len");
-  if (max_label_len > wk::kCtcAlignMaxLabels) return invalid("wk_ctc_align: max_label_len > 255");
-  if (vocab > wk::kCtcAlignMaxVocab) return invalid("wk_ctc_align: vocab > 65536");
-  if (batch * T > wk::kCtcAlignMaxFrames || batch > wk::kCtcAlignMaxFrames) return invalid("wk_ctc_align: batch * T > 2^28");
+  if (max_label_len > wk::kCtcLatticeMaxLabels) return invalid("wk_ctc_align: max_label_len > 255");
+  if (vocab > wk::kCtcMaxVocab) return invalid("wk_ctc_align: vocab > 65536");
+  if (batch * T > wk::kCtcMaxFrames || batch > wk::kCtcMaxFrames) return invalid("wk_ctc_align: batch * T > 2^28");
   if ((uintptr_t)d_workspace & 15) return invalid("wk_ctc_align: d_workspace must be 16-byte aligned");
   if (device < 0) return invalid("wk_ctc_align: device < 0");
   const wk::CtcAlignWs w = wk::ctc_align_layout(d_workspace, batch, T, max_label_len);
@@ -354,24 +272,17 @@ wk_status wk_ctc_align(const float* d_log_probs, int64_t batch, int32_t T, int32
   return wk::on_device(device, [&]() -> wk_status {
     hipLaunchKernelGGL(wk::ctc_align_prep_kernel, dim3((unsigned)batch), dim3(256), 0, st, d_labels, label_stride,
                        d_input_lengths, d_label_lengths, T, vocab, max_label_len, d_spans_or_null, w);
-    int shift = 6;
-    while ((1 << shift) < w.ls) ++shift;
-    const int64_t total = batch * T * w.ls;
-    hipLaunchKernelGGL(wk::ctc_align_gather_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, d_log_probs, T,
-                       vocab, shift, total, w);
-    switch (w.ls / 64) {
-      case 1: wk::launch_recur<1>(batch, T, w, d_states, d_score, st); break;
-      case 2: wk::launch_recur<2>(batch, T, w, d_states, d_score, st); break;
-      case 4: wk::launch_recur<4>(batch, T, w, d_states, d_score, st); break;
-      default: wk::launch_recur<8>(batch, T, w, d_states, d_score, st); break;
-    }
+    wk::launch_lattice_gather(d_log_probs, batch, T, vocab, w, st);
+    wk::dispatch_R(w.ls, [&](auto r) {
+      hipLaunchKernelGGL(wk::ctc_align_recur_kernel<decltype(r)::value>, dim3((unsigned)batch), dim3(64), 0, st, T, w, d_states,
+                         d_score);
+    });
     if (d_frame_tokens_or_null || d_frame_lp_or_null || d_spans_or_null) {
       const int64_t frames = batch * T;
       hipLaunchKernelGGL(wk::ctc_align_emit_kernel, dim3((unsigned)((frames + 255) / 256)), dim3(256), 0, st, d_states, T,
                          max_label_len, frames, d_frame_tokens_or_null, d_frame_lp_or_null, d_spans_or_null, w);
     }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? WK_OK : hip_fail(e, "wk_ctc_align launch");
+    return wk::ctc_launched("wk_ctc_align");
   });
 }
 

@@ -6,10 +6,10 @@
 //
 // Two launches on the caller's stream, no host synchronisation, no atomics:
 //   cand    one wave per (b, t) row.  The row is read once, 16 bytes per lane
-//           where it is 16-byte aligned (head and tail elements singly, so no
-//           byte outside the row is touched).  The K best (value, id) pairs so
-//           far live one per lane, sorted; an element enters only if it beats
-//           the K-th (value greater, or equal with the lower id: compares only),
+//           where it is 16-byte aligned (RowSplit, wk_ctc_lattice_dev.h).  The
+//           K best (value, id) pairs so far live one per lane, sorted; an
+//           element enters only if it beats the K-th (value greater, or equal
+//           with the lower id: compares only),
 //           which a wave-wide ballot decides for 256 elements at a time, so the
 //           common chunk costs one max and one compare per lane.  An insertion
 //           is a lane shift (DPP) of the pairs behind it.  The wave writes C_t
@@ -37,21 +37,18 @@
 //                     (parent id, token): one row of up to W words per frame.
 //           After the last frame lane i < n_best walks its chain up the table
 //           into d_tokens.
-// (+) = max + log(1 + exp(min - max)) with v_exp_f32 / v_log_f32; every sum has
-// one fixed order, so equal inputs give equal bits.
+// (+) is lse2 (wk_ctc_lattice_dev.h); every sum has one fixed order, so equal
+// inputs give equal bits.
 #include <math.h>
 
 #include "wakeword.h"
-#include "wk_common.h"
-#include "wk_kernels.h"
+#include "wk_ctc_lattice_dev.h"
 
 namespace wk {
 namespace {
 
 constexpr int kCtcBeamMaxBeam = 64;          // one lane per slot
 constexpr int kCtcBeamMaxTopK = 32;          // one register per extension
-constexpr int kCtcBeamMaxVocab = 65536;      // a token is 16 bits of a node word
-constexpr int64_t kCtcBeamMaxFrames = (int64_t)1 << 28;   // batch * T
 constexpr int kNoId = 0x7FFFFFFF;            // an empty entry of the candidate list: loses to every id
 
 struct CtcBeamWs {
@@ -69,23 +66,9 @@ CtcBeamWs ctc_beam_layout(void* base, int64_t batch, int32_t T, int32_t beam, in
   w.cid = (int32_t*)(w.nodes + frames * beam + batch);
   w.cval = (float*)(w.cid + frames * top_k);
   w.blank = w.cval + frames * top_k;
-  w.bytes = 8 * (frames * beam + batch) + 4 * (2 * frames * top_k + frames);
-  w.bytes = (w.bytes + 255) & ~(int64_t)255;
+  w.bytes = round_up_256(8 * (frames * beam + batch) + 4 * (2 * frames * top_k + frames));
   return w;
 }
-
-__device__ __forceinline__ float neg_inf() { return -__builtin_inff(); }
-
-__device__ __forceinline__ int rl(int v, int lane) { return __builtin_amdgcn_readlane(v, lane); }
-__device__ __forceinline__ float rl(float v, int lane) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane)); }
-__device__ __forceinline__ uint32_t rl(uint32_t v, int lane) { return (uint32_t)__builtin_amdgcn_readlane((int)v, lane); }
-__device__ __forceinline__ int64_t rl(int64_t v, int lane) {
-  const uint32_t lo = rl((uint32_t)v, lane), hi = rl((uint32_t)((uint64_t)v >> 32), lane);
-  return (int64_t)(((uint64_t)hi << 32) | lo);
-}
-
-// The previous lane's value (wave_shr:1); lane 0 keeps `first`.
-__device__ __forceinline__ int prev_lane(int first, int v) { return __builtin_amdgcn_update_dpp(first, v, 0x138, 0xF, 0xF, false); }
 
 // (v, id) ranks before (w, jd): the greater value, or an equal one with the lower id.
 __device__ __forceinline__ bool beats(float v, int id, float w, int jd) { return v > w || (v == w && id < jd); }
@@ -104,17 +87,17 @@ __device__ __forceinline__ void offer(TopList& s, float v, int id, bool valid, i
   uint64_t m;
   while ((m = __ballot(pend)) != 0) {
     const int l = __builtin_ctzll(m);
-    const float xv = rl(v, l);
-    const int xid = rl(id, l);
-    const float pv = __int_as_float(prev_lane(0, __float_as_int(s.kv)));
+    const float xv = read_lane(v, l);
+    const int xid = read_lane(id, l);
+    const float pv = prev_lane(0.0f, s.kv);
     const int pid = prev_lane(0, s.kid);
     if (beats(xv, xid, s.kv, s.kid)) {                           // x goes in front of this lane's pair:
       const bool behind = lane > 0 && beats(xv, xid, pv, pid);   // ... and of the previous lane's, which moves here
       s.kv = behind ? pv : xv;
       s.kid = behind ? pid : xid;
     }
-    s.tv = rl(s.kv, K - 1);
-    s.tid = rl(s.kid, K - 1);
+    s.tv = read_lane(s.kv, K - 1);
+    s.tid = read_lane(s.kid, K - 1);
     pend = pend && lane != l && beats(v, id, s.tv, s.tid);
   }
 }
@@ -133,16 +116,14 @@ __global__ __launch_bounds__(256) void ctc_beam_cand_kernel(const float* __restr
   }
   const float* p = lp + row * V;
   TopList s = {neg_inf(), kNoId, neg_inf(), kNoId};
-  // The row as head (up to the first 16-byte boundary), quads, tail: ids 0 .. V-1 in order.
-  const int head = min((int)((4 - (((uintptr_t)p >> 2) & 3)) & 3), V);
-  const int nq = (V - head) >> 2;
-  const int tail0 = head + 4 * nq;
+  const RowSplit r = row_split(p, V);
+  const int head = r.head, nq = r.nq, tail0 = r.tail0;
   if (head) {
     const bool in = lane < head;
     offer(s, p[min(lane, head - 1)], lane, in && lane != 0, K, lane);
   }
   // Quads: a lane past the last one re-reads the last (an address inside the row; `in` keeps it out of the ranking).
-  const float4* q4 = reinterpret_cast<const float4*>(p + head);
+  const float4* q4 = r.q4;
   if (nq > 0) {
     float4 cur = q4[min(lane, nq - 1)];
     for (int base = 0; base < nq; base += 64) {
@@ -169,7 +150,7 @@ __global__ __launch_bounds__(256) void ctc_beam_cand_kernel(const float* __restr
   // lanes 0 .. nv-1 hold C_t in selection order; the workspace takes it sorted by id
   const bool have = lane < K && s.kid != kNoId;
   int pos = 0;
-  for (int j = 0; j < K; ++j) pos += rl(s.kid, j) < s.kid;
+  for (int j = 0; j < K; ++j) pos += read_lane(s.kid, j) < s.kid;
   if (!have) pos = lane;                                    // (the empty entries stay behind the nv valid ones)
   if (lane < K) {
     if (cand_out) cand_out[row * K + lane] = have ? s.kid : -1;
@@ -180,24 +161,6 @@ __global__ __launch_bounds__(256) void ctc_beam_cand_kernel(const float* __restr
 }
 
 // ---- beam recurrence ----------------------------------------------------------------
-// log(exp(a) + exp(b)); -inf for two -inf.
-__device__ __forceinline__ float lse2(float a, float b) {
-  const float m = fmaxf(a, b), d = fminf(a, b) - m;
-  const float r = m + __builtin_amdgcn_logf(1.0f + __builtin_amdgcn_exp2f(d * 1.44269504088896341f)) * 0.69314718055994531f;
-  return m == neg_inf() ? m : r;
-}
-
-template <int CTRL> __device__ __forceinline__ float max_dpp(float v) { return fmaxf(v, dpp<CTRL>(v)); }
-
-// Maximum over the 64 lanes, in every lane (wave_sum's butterflies with max).  All lanes active.
-__device__ __forceinline__ float wave_max(float v) {
-  v = max_dpp<0xB1>(v);
-  v = max_dpp<0x4E>(v);
-  v = max_dpp<0x141>(v);
-  v = max_dpp<0x140>(v);
-  return fmaxf(fmaxf(rl(v, 0), rl(v, 16)), fmaxf(rl(v, 32), rl(v, 48)));
-}
-
 constexpr uint32_t kHashRoot = 0x811C9DC5u;
 __device__ __forceinline__ uint32_t hash_next(uint32_t h, int token) {
   h = (h ^ (uint32_t)(token + 1)) * 0x01000193u;
@@ -256,16 +219,16 @@ __global__ __launch_bounds__(64) void ctc_beam_recur_kernel(const float* __restr
     const int e_or_none = e > 0 ? e : -2;
     int kpos = -1;
 #pragma unroll
-    for (int k = 0; k < KMAX; ++k) kpos = rl(cidr, k) == e_or_none ? k : kpos;
+    for (int k = 0; k < KMAX; ++k) kpos = read_lane(cidr, k) == e_or_none ? k : kpos;
 
     // merge: lane j finds the live i whose extension by e_j is j's prefix
     float merge_from = neg_inf();       // the mass lane j's prefix takes from the extension that equals it, before lp[e]
     uint32_t merged = 0;                // bit k: this lane's extension by candidate k is a live prefix
     for (int i = 0; i < nlive; ++i) {
-      const uint32_t hi = rl(h, i);
-      const int leni = rl(len, i), ei = rl(e, i);
-      const int64_t nodei = rl(node, i);
-      const float pbi = rl(pb, i), pi = rl(p, i);
+      const uint32_t hi = read_lane(h, i);
+      const int leni = read_lane(len, i), ei = read_lane(e, i);
+      const int64_t nodei = read_lane(node, i);
+      const float pbi = read_lane(pb, i), pi = read_lane(p, i);
       bool hit = live && kpos >= 0 && len == leni + 1 && ph == hi;
       if (__ballot(hit && par != nodei) != 0) {                      // (rare: the parent prefix was made twice, or the hashes collide)
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");      // other lanes' node words
@@ -276,7 +239,7 @@ __global__ __launch_bounds__(64) void ctc_beam_recur_kernel(const float* __restr
         if (hit) merge_from = e == ei ? pbi : pi;
         do {
           const int j = __builtin_ctzll(m);
-          const int kb = rl(kpos, j);
+          const int kb = read_lane(kpos, j);
           if (lane == i) merged |= 1u << kb;
           m &= m - 1;
         } while (m != 0);
@@ -294,8 +257,8 @@ __global__ __launch_bounds__(64) void ctc_beam_recur_kernel(const float* __restr
     float ext[KMAX];
 #pragma unroll
     for (int k = 0; k < KMAX; ++k) {      // (k >= K: id -1, value -inf)
-      const int ck = rl(cidr, k);
-      const float cv = rl(cvalr, k);
+      const int ck = read_lane(cidr, k);
+      const float cv = read_lane(cvalr, k);
       ext[k] = live && ck > 0 && !((merged >> k) & 1u) ? cv + (ck == e ? pb : p) : neg_inf();
     }
     float best = stot;
@@ -317,18 +280,18 @@ __global__ __launch_bounds__(64) void ctc_beam_recur_kernel(const float* __restr
       const uint64_t ma = __ballot(best == wmax), ms = __ballot(best == wmax && bk < 0);
       if (ma == 0) break;
       const int win = __builtin_ctzll(ms != 0 ? ms : ma);
-      const int kw = rl(bk, win);
-      const int64_t nodew = rl(node, win);
-      const uint32_t hw = rl(h, win);
-      const int lenw = rl(len, win);
+      const int kw = read_lane(bk, win);
+      const int64_t nodew = read_lane(node, win);
+      const uint32_t hw = read_lane(h, win);
+      const int lenw = read_lane(len, win);
       if (kw < 0) {
-        const float a = rl(spb, win), c = rl(spnb, win);
-        const int ew = rl(e, win);
-        const int64_t parw = rl(par, win);
-        const uint32_t phw = rl(ph, win);
+        const float a = read_lane(spb, win), c = read_lane(spnb, win);
+        const int ew = read_lane(e, win);
+        const int64_t parw = read_lane(par, win);
+        const uint32_t phw = read_lane(ph, win);
         if (lane == r) n_pb = a, n_pnb = c, n_p = wmax, n_e = ew, n_len = lenw, n_node = nodew, n_par = parw, n_h = hw, n_ph = phw;
       } else {
-        const int tok = rl(cidr, kw);
+        const int tok = read_lane(cidr, kw);
         if (lane == r) {
           n_pb = neg_inf(), n_pnb = wmax, n_p = wmax, n_e = tok, n_len = lenw + 1;
           n_node = (int64_t)t * W + r + 1, n_par = nodew, n_h = hash_next(hw, tok), n_ph = hw;
@@ -361,7 +324,7 @@ __global__ __launch_bounds__(64) void ctc_beam_recur_kernel(const float* __restr
     scores[out0 + lane] = lane < nlive ? p : neg_inf();
   }
   for (int i = 0; i < n_best; ++i) {                     // -1 beyond each length
-    const int li = i < nlive ? min(rl(len, i), max_len) : 0;
+    const int li = i < nlive ? min(read_lane(len, i), max_len) : 0;
     int32_t* row = tokens + (out0 + i) * max_len;
     for (int x = li + lane; x < max_len; x += 64) row[x] = -1;
   }
@@ -386,14 +349,13 @@ void launch_recur(const float* lp, const int32_t* in_len, int64_t batch, int T, 
 }  // namespace
 }  // namespace wk
 
-using wk::hip_fail;
 using wk::invalid;
 
 extern "C" {
 
 int64_t wk_ctc_beam_workspace_bytes(int64_t batch, int32_t T, int32_t beam, int32_t top_k) {
   if (batch <= 0 || T <= 0 || beam < 1 || beam > wk::kCtcBeamMaxBeam || top_k < 1 || top_k > wk::kCtcBeamMaxTopK ||
-      batch > wk::kCtcBeamMaxFrames || batch * T > wk::kCtcBeamMaxFrames)
+      batch > wk::kCtcMaxFrames || batch * T > wk::kCtcMaxFrames)
     return 0;
   return wk::ctc_beam_layout(nullptr, batch, T, beam, top_k).bytes;
 }
@@ -403,12 +365,12 @@ wk_status wk_ctc_beam(const float* d_log_probs, int64_t batch, int32_t T, int32_
                       int32_t* d_lengths, float* d_scores, int32_t* d_cand_or_null, int32_t device, void* stream) {
   if (!d_log_probs || !d_workspace || !d_tokens || !d_lengths || !d_scores) return invalid("wk_ctc_beam: null pointer");
   if (batch <= 0 || T <= 0) return invalid("wk_ctc_beam: batch and T must be positive");
-  if (vocab < 2 || vocab > wk::kCtcBeamMaxVocab) return invalid("wk_ctc_beam: vocab must be in [2, 65536]");
+  if (vocab < 2 || vocab > wk::kCtcMaxVocab) return invalid("wk_ctc_beam: vocab must be in [2, 65536]");
   if (beam < 1 || beam > wk::kCtcBeamMaxBeam) return invalid("wk_ctc_beam: beam must be in [1, 64]");
   if (top_k < 1 || top_k > wk::kCtcBeamMaxTopK) return invalid("wk_ctc_beam: top_k must be in [1, 32]");
   if (n_best < 1 || n_best > beam) return invalid("wk_ctc_beam: n_best must be in [1, beam]");
   if (max_len < 1) return invalid("wk_ctc_beam: max_len < 1");
-  if (batch > wk::kCtcBeamMaxFrames || batch * T > wk::kCtcBeamMaxFrames) return invalid("wk_ctc_beam: batch * T > 2^28");
+  if (batch > wk::kCtcMaxFrames || batch * T > wk::kCtcMaxFrames) return invalid("wk_ctc_beam: batch * T > 2^28");
   if ((uintptr_t)d_workspace & 15) return invalid("wk_ctc_beam: d_workspace must be 16-byte aligned");
   if (device < 0) return invalid("wk_ctc_beam: device < 0");
   const wk::CtcBeamWs w = wk::ctc_beam_layout(d_workspace, batch, T, beam, top_k);
@@ -426,8 +388,7 @@ wk_status wk_ctc_beam(const float* d_log_probs, int64_t batch, int32_t T, int32_
     else
       wk::launch_recur<32>(d_log_probs, d_input_lengths_or_null, batch, T, vocab, beam, top_k, n_best, max_len, w, d_tokens,
                            d_lengths, d_scores, st);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? WK_OK : hip_fail(e, "wk_ctc_beam launch");
+    return wk::ctc_launched("wk_ctc_beam");
   });
 }
 

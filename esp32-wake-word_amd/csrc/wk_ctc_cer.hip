@@ -41,8 +41,7 @@
 // The workspace holds (N, M) per pair and nothing proportional to
 // hyp_stride * max_ref_len: no DP matrix, no back-pointers.
 #include "wakeword.h"
-#include "wk_common.h"
-#include "wk_kernels.h"
+#include "wk_ctc_lattice_dev.h"
 
 namespace wk {
 namespace {
@@ -63,7 +62,7 @@ bool cer_shape_ok(int64_t batch, int32_t n_hyp, int32_t hyp_stride, int32_t max_
 }
 
 int64_t cer_bytes(int64_t batch, int32_t n_hyp) {       // (N, M) [batch][n_hyp]
-  return (8 * batch * n_hyp + 255) & ~(int64_t)255;
+  return round_up_256(8 * batch * n_hyp);
 }
 
 // v of the lane `n` below in the same row of 16 lanes (row_shr:n); kCerInf where there is none.
@@ -73,7 +72,7 @@ template <int N> __device__ __forceinline__ int min_row_shr(int v) {
 
 // min over the lanes below this one (kCerInf in lane 0).  All 64 lanes active.
 __device__ __forceinline__ int wave_prefix_min_excl(int m, int lane) {
-  int v = __builtin_amdgcn_update_dpp(kCerInf, m, 0x138, 0xF, 0xF, false);    // wave_shr:1
+  int v = prev_lane(kCerInf, m);
   v = min_row_shr<1>(v);
   v = min_row_shr<2>(v);
   v = min_row_shr<4>(v);
@@ -118,7 +117,7 @@ __global__ __launch_bounds__(64) void ctc_cer_pairs_kernel(const int32_t* __rest
     next = tn < len ? hp[tn] : 0;
     uint64_t keep;
     if (collapse) {
-      const int before = __builtin_amdgcn_update_dpp(carry, cur, 0x138, 0xF, 0xF, false);   // wave_shr:1, lane 0: the carry
+      const int before = prev_lane(carry, cur);    // (lane 0: the carry)
       keep = __ballot(t0 + lane < len && cur != 0 && cur != before);
       carry = __builtin_amdgcn_readlane(cur, 63);  // (only read when a next chunk exists: this one was full)
     } else {
@@ -129,7 +128,7 @@ __global__ __launch_bounds__(64) void ctc_cer_pairs_kernel(const int32_t* __rest
       keep &= keep - 1;
       const int h = __builtin_amdgcn_readlane(cur, src);
       // D[i-1][l C] - (l C) DEL for the lane's first column; lane 0: column 0 of the row before, N INS
-      const int left = __builtin_amdgcn_update_dpp(N * kCerIns, w[C - 1], 0x138, 0xF, 0xF, false);
+      const int left = prev_lane(N * kCerIns, w[C - 1]);
       int p[C];
 #pragma unroll
       for (int q = 0; q < C; ++q) {
@@ -207,7 +206,6 @@ __global__ __launch_bounds__(kCerReduceBlock) void ctc_cer_reduce_kernel(const i
 }  // namespace
 }  // namespace wk
 
-using wk::hip_fail;
 using wk::invalid;
 
 extern "C" {
@@ -249,8 +247,7 @@ wk_status wk_ctc_cer(const int32_t* d_hyp, const int32_t* d_hyp_lengths_or_null,
     if (d_best_or_null || d_totals_or_null)
       hipLaunchKernelGGL(wk::ctc_cer_reduce_kernel, dim3(1), dim3(wk::kCerReduceBlock), 0, st, (const int32_t*)d_stats,
                          (const int32_t*)nm, batch, n_hyp, d_best_or_null, d_totals_or_null);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? WK_OK : hip_fail(e, "wk_ctc_cer launch");
+    return wk::ctc_launched("wk_ctc_cer");
   });
 }
 

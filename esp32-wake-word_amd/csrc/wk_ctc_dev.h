@@ -10,6 +10,10 @@
 //   wk_ctc_bwd.hip     the fp32 backward pass: parameter gradients from the gradient at the logits
 //   wk_ctc_optim.hip   clip + Adam on the handle's weights, the W_hh fragments again, blob <-> buffers
 //
+// The units that consume the head's [B][T][V] log-probs have their own ABI and
+// no launcher here: wk_ctc_loss.hip, wk_ctc_align.hip, wk_ctc_beam.hip,
+// wk_ctc_spot.hip, wk_ctc_cer.hip.  What those share is wk_ctc_lattice_dev.h.
+//
 // Layout constants stay with the kernel that defines the layout: each packer
 // and each grid computation sits in the kernel's own unit, so none is needed
 // here.  A launcher that only enqueues kernels returns nothing: a launch error

@@ -10,15 +10,13 @@
 // torch's native CTC backward convention (both alpha and beta include lp_t).
 //
 // Five launches on the caller's stream, no host synchronisation:
-//   prep     one block per utterance: lengths clamped, labels validated and
-//            copied, and the states of one class chained in index order;
-//   gather   lp_t(l'_s) into a dense [B][T][Ls] buffer, parallel over t, so the
-//            recursion never waits on a strided load from a V-wide row;
-//   recur    one wave per (utterance, direction): lane i holds the R = Ls/64
-//            consecutive states i*R .. i*R+R-1 in registers, so the neighbours
-//            s-1, s-2 (s+1, s+2) are its own registers but for two values that
-//            come from the next lane by a DPP wave shift -- no LDS, no barrier;
-//            the gathered rows are loaded a group of steps ahead;
+//   prep     one block per utterance: the lattice's inputs (lengths, labels:
+//            wk_ctc_lattice_dev.h), and the states of one class chained in
+//            index order;
+//   gather   lp_t(l'_s) into a dense [B][T][Ls] buffer (wk_ctc_lattice_dev.h);
+//   recur    one wave per (utterance, direction) on the register-row layout of
+//            wk_ctc_lattice_dev.h -- no LDS, no barrier; the gathered rows are
+//            loaded a group of steps ahead;
 //   grad     one block per (b, t): alpha + beta staged in LDS, each class's
 //            states summed by one lane in index order (the blank's by one wave,
 //            a fixed butterfly), the V-wide row written with 16-byte accesses;
@@ -27,15 +25,11 @@
 #include <math.h>
 
 #include "wakeword.h"
-#include "wk_common.h"
-#include "wk_kernels.h"
+#include "wk_ctc_lattice_dev.h"
 
 namespace wk {
 namespace {
 
-constexpr int kCtcLossMaxLabels = 255;      // L = 511 states: 8 registers per lane
-constexpr int kCtcLossMaxVocab = 65536;
-constexpr int64_t kCtcLossMaxFrames = (int64_t)1 << 28;   // batch * T: one grad block per frame
 constexpr int kFirst = 0x10000;             // chain code: bit 16 = first state of its class, low 16 = next + 1
 
 struct CtcLossWs {
@@ -45,17 +39,9 @@ struct CtcLossWs {
   int64_t bytes;
 };
 
-// States per row, rounded to 64 R with R in {1, 2, 4, 8}; 0 beyond the limit.
-int ctc_loss_row(int max_label_len) {
-  const int L = 2 * max_label_len + 1;
-  for (int r = 1; r <= 8; r *= 2)
-    if (L <= 64 * r) return 64 * r;
-  return 0;
-}
-
 CtcLossWs ctc_loss_layout(void* base, int64_t batch, int32_t T, int32_t max_label_len) {
   CtcLossWs w;
-  w.ls = ctc_loss_row(max_label_len);
+  w.ls = ctc_lattice_row(max_label_len);
   w.smax = max_label_len > 0 ? max_label_len : 1;
   const int64_t rows = batch * T * w.ls;
   float* f = (float*)base;
@@ -66,12 +52,9 @@ CtcLossWs ctc_loss_layout(void* base, int64_t batch, int32_t T, int32_t max_labe
   w.meta = (int32_t*)(w.nll + batch);
   w.lab = w.meta + 4 * batch;
   w.chain = w.lab + batch * w.smax;
-  w.bytes = (int64_t)sizeof(float) * (3 * rows + batch) + (int64_t)sizeof(int32_t) * (4 * batch + 2 * batch * w.smax);
-  w.bytes = (w.bytes + 255) & ~(int64_t)255;
+  w.bytes = round_up_256((int64_t)sizeof(float) * (3 * rows + batch) + (int64_t)sizeof(int32_t) * (4 * batch + 2 * batch * w.smax));
   return w;
 }
-
-__device__ __forceinline__ float neg_inf() { return -__builtin_inff(); }
 
 // ---- prep -------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void ctc_loss_prep_kernel(const int32_t* __restrict__ labels, int label_stride,
@@ -80,17 +63,10 @@ __global__ __launch_bounds__(256) void ctc_loss_prep_kernel(const int32_t* __res
                                                             CtcLossWs w) {
   __shared__ int sl[256];
   const int b = blockIdx.x, i = threadIdx.x;
-  const int Tb = min(max(in_len[b], 0), T);
-  const int S = min(max(lab_len[b], 0), max_label_len);
-  int v = 0, bad = 0;
-  if (i < S) {
-    v = labels[(int64_t)b * label_stride + i];
-    bad = v < 1 || v >= V;
-    if (bad) v = 0;                          // never an index; the utterance gets nll = +inf
-    w.lab[(int64_t)b * w.smax + i] = v;
-  }
+  const LatticePrep p = lattice_prep_labels(labels, label_stride, in_len, lab_len, T, V, max_label_len, w);
+  const int S = p.S, v = p.v;
   sl[i] = i < S ? v : -1;
-  const int any_bad = __syncthreads_or(bad);
+  const int any_bad = __syncthreads_or(p.bad);
   if (i < S) {
     int first = kFirst, next = 0;
     for (int j = 0; j < i; ++j)
@@ -99,110 +75,22 @@ __global__ __launch_bounds__(256) void ctc_loss_prep_kernel(const int32_t* __res
       if (sl[j] == v) next = j + 1;
     w.chain[(int64_t)b * w.smax + i] = first | next;
   }
-  if (i == 0) {
-    w.meta[4 * b + 0] = Tb;
-    w.meta[4 * b + 1] = S;
-    w.meta[4 * b + 2] = !any_bad;
-    w.meta[4 * b + 3] = 0;
-  }
-}
-
-// ---- gather -----------------------------------------------------------------------
-__global__ __launch_bounds__(256) void ctc_loss_gather_kernel(const float* __restrict__ lp, int T, int V, int ls_shift, int64_t total,
-                                                              CtcLossWs w) {
-  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= total) return;                                        // total = batch * T * ls
-  const int s = (int)(idx & (w.ls - 1));
-  const int64_t bt = idx >> ls_shift;
-  const int b = (int)(bt / T), t = (int)(bt % T);
-  const int Tb = w.meta[4 * b], S = w.meta[4 * b + 1];
-  if (t >= Tb) return;
-  if (s > 2 * S) {                 // past the last state: -inf, which the recursion relies on
-    w.lpg[idx] = neg_inf();
-    return;
-  }
-  const int v = (s & 1) ? w.lab[(int64_t)b * w.smax + (s >> 1)] : 0;
-  w.lpg[idx] = lp[bt * V + v];
+  lattice_prep_meta(p.Tb, S, any_bad, w);
+  if (i == 0) w.meta[4 * b + 3] = 0;
 }
 
 // ---- recursion --------------------------------------------------------------------
-template <int R> __device__ __forceinline__ void ld_row(const float* p, float (&r)[R]) {
-  if constexpr (R == 1) {
-    r[0] = p[0];
-  } else if constexpr (R == 2) {
-    const float2 v = *reinterpret_cast<const float2*>(p);
-    r[0] = v.x;
-    r[1] = v.y;
-  } else {
-#pragma unroll
-    for (int k = 0; k < R / 4; ++k) {
-      const float4 v = reinterpret_cast<const float4*>(p)[k];
-      r[4 * k] = v.x, r[4 * k + 1] = v.y, r[4 * k + 2] = v.z, r[4 * k + 3] = v.w;
-    }
-  }
-}
-template <int R> __device__ __forceinline__ void st_row(float* p, const float (&r)[R]) {
-  if constexpr (R == 1) {
-    p[0] = r[0];
-  } else if constexpr (R == 2) {
-    *reinterpret_cast<float2*>(p) = make_float2(r[0], r[1]);
-  } else {
-#pragma unroll
-    for (int k = 0; k < R / 4; ++k) reinterpret_cast<float4*>(p)[k] = make_float4(r[4 * k], r[4 * k + 1], r[4 * k + 2], r[4 * k + 3]);
-  }
-}
-
-// The value of the previous (wave_shr:1) / next (wave_shl:1) lane; -inf where there is none.
-__device__ __forceinline__ float from_prev_lane(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(neg_inf()), __float_as_int(v), 0x138, 0xF, 0xF, false));
-}
-__device__ __forceinline__ float from_next_lane(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(neg_inf()), __float_as_int(v), 0x130, 0xF, 0xF, false));
-}
-
-// ln(e^a + e^b) and ln(e^a + e^b + e^c), -inf when every term is.  The largest
-// term's exponential is 1 exactly, so it is not computed: max / med / min are
-// one instruction each where an exponential is a double-cost one.  (All -inf:
-// the differences are NaN and the select drops them.)
-__device__ __forceinline__ float lse2(float a, float b) {
-  const float m = fmaxf(a, b), n = fminf(a, b);
-  const float r = m + wk_logf(1.0f + __expf(n - m));
-  return m == neg_inf() ? m : r;
-}
-__device__ __forceinline__ float lse3(float a, float b, float c) {
-  const float m = fmaxf(fmaxf(a, b), c), d = __builtin_amdgcn_fmed3f(a, b, c), n = fminf(fminf(a, b), c);
-  const float r = m + wk_logf(1.0f + __expf(d - m) + __expf(n - m));
-  return m == neg_inf() ? m : r;
-}
-
 // One step of the recursion: a <- x + lse(a, the neighbours'), x the gathered row
 // (-inf at s >= L, which keeps those states at -inf).
 template <int R, bool REV>
 __device__ __forceinline__ void ctc_loss_step(float (&a)[R], const float (&x)[R], const bool (&skip)[R]) {
-  float n1[R], n2[R];
-  if constexpr (!REV) {
-    const float p1 = from_prev_lane(a[R - 1]);
-    const float p2 = R >= 2 ? from_prev_lane(a[R >= 2 ? R - 2 : 0]) : from_prev_lane(p1);
-#pragma unroll
-    for (int j = 0; j < R; ++j) {
-      n1[j] = j >= 1 ? a[j >= 1 ? j - 1 : 0] : p1;
-      n2[j] = j >= 2 ? a[j >= 2 ? j - 2 : 0] : (j == 1 ? p1 : p2);
-    }
-  } else {
-    const float q1 = from_next_lane(a[0]);
-    const float q2 = R >= 2 ? from_next_lane(a[R >= 2 ? 1 : 0]) : from_next_lane(q1);
-#pragma unroll
-    for (int j = 0; j < R; ++j) {
-      n1[j] = j + 1 < R ? a[j + 1 < R ? j + 1 : 0] : q1;
-      n2[j] = j + 2 < R ? a[j + 2 < R ? j + 2 : 0] : (j + 2 == R ? q1 : q2);
-    }
-  }
+  const LatticeNb<R> n = lattice_neighbours<R, REV>(a);
 #pragma unroll
   for (int j = 0; j < R; ++j) {
     if (R % 2 == 0 && j % 2 == 0)      // s = lane R + j is even: a blank, two terms
-      a[j] = x[j] + lse2(a[j], n1[j]);
+      a[j] = x[j] + lse2(a[j], n.n1[j]);
     else
-      a[j] = x[j] + lse3(a[j], n1[j], skip[j] ? n2[j] : neg_inf());
+      a[j] = x[j] + lse3(a[j], n.n1[j], skip[j] ? n.n2[j] : neg_inf());
   }
 }
 
@@ -313,7 +201,7 @@ __global__ __launch_bounds__(64) void ctc_loss_recur_kernel(int T, CtcLossWs w) 
 template <bool VEC>
 __global__ __launch_bounds__(256) void ctc_loss_grad_kernel(const float* __restrict__ lp, float* __restrict__ grad, int T, int V,
                                                             int64_t batch, int mean, float grad_scale, CtcLossWs w) {
-  __shared__ float ab[2 * kCtcLossMaxLabels + 2];
+  __shared__ float ab[2 * kCtcLatticeMaxLabels + 2];
   __shared__ int chain[256];
   __shared__ float blank_lcab;
   const int64_t bt = blockIdx.x;
@@ -405,21 +293,15 @@ __global__ __launch_bounds__(256) void ctc_loss_finish_kernel(int64_t batch, int
   if (tid == 0) d_loss[0] = (float)(reduction == WK_CTC_REDUCTION_MEAN ? part[0] / (double)batch : part[0]);
 }
 
-template <int R> void launch_recur(int64_t batch, int T, const CtcLossWs& w, hipStream_t st) {
-  hipLaunchKernelGGL(ctc_loss_recur_kernel<R>, dim3((unsigned)(2 * batch)), dim3(64), 0, st, T, w);
-}
-
 }  // namespace
 }  // namespace wk
 
-using wk::hip_fail;
 using wk::invalid;
 
 extern "C" {
 
 int64_t wk_ctc_loss_workspace_bytes(int64_t batch, int32_t T, int32_t max_label_len) {
-  if (batch <= 0 || T <= 0 || max_label_len < 0 || max_label_len > wk::kCtcLossMaxLabels || batch * T > wk::kCtcLossMaxFrames)
-    return 0;
+  if (!wk::ctc_lattice_shape_ok(batch, T, max_label_len)) return 0;
   return wk::ctc_loss_layout(nullptr, batch, T, max_label_len).bytes;
 }
 
@@ -433,9 +315,9 @@ wk_status wk_ctc_loss(const float* d_log_probs, int64_t batch, int32_t T, int32_
   if (max_label_len < 0 || label_stride < max_label_len) return invalid("wk_ctc_loss: label_stride < max_label_len");
   if (reduction != WK_CTC_REDUCTION_NONE && reduction != WK_CTC_REDUCTION_SUM && reduction != WK_CTC_REDUCTION_MEAN)
     return invalid("wk_ctc_loss: bad reduction");
-  if (max_label_len > wk::kCtcLossMaxLabels) return invalid("wk_ctc_loss: max_label_len > 255");
-  if (vocab > wk::kCtcLossMaxVocab) return invalid("wk_ctc_loss: vocab > 65536");
-  if (batch * T > wk::kCtcLossMaxFrames || batch > wk::kCtcLossMaxFrames) return invalid("wk_ctc_loss: batch * T > 2^28");
+  if (max_label_len > wk::kCtcLatticeMaxLabels) return invalid("wk_ctc_loss: max_label_len > 255");
+  if (vocab > wk::kCtcMaxVocab) return invalid("wk_ctc_loss: vocab > 65536");
+  if (batch * T > wk::kCtcMaxFrames || batch > wk::kCtcMaxFrames) return invalid("wk_ctc_loss: batch * T > 2^28");
   if ((uintptr_t)d_workspace & 15) return invalid("wk_ctc_loss: d_workspace must be 16-byte aligned");
   if (device < 0) return invalid("wk_ctc_loss: device < 0");
   const wk::CtcLossWs w = wk::ctc_loss_layout(d_workspace, batch, T, max_label_len);
@@ -443,17 +325,10 @@ wk_status wk_ctc_loss(const float* d_log_probs, int64_t batch, int32_t T, int32_
   return wk::on_device(device, [&]() -> wk_status {
     hipLaunchKernelGGL(wk::ctc_loss_prep_kernel, dim3((unsigned)batch), dim3(256), 0, st, d_labels, label_stride, d_input_lengths,
                        d_label_lengths, T, vocab, max_label_len, w);
-    int shift = 6;
-    while ((1 << shift) < w.ls) ++shift;
-    const int64_t total = batch * T * w.ls;
-    hipLaunchKernelGGL(wk::ctc_loss_gather_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, d_log_probs, T,
-                       vocab, shift, total, w);
-    switch (w.ls / 64) {
-      case 1: wk::launch_recur<1>(batch, T, w, st); break;
-      case 2: wk::launch_recur<2>(batch, T, w, st); break;
-      case 4: wk::launch_recur<4>(batch, T, w, st); break;
-      default: wk::launch_recur<8>(batch, T, w, st); break;
-    }
+    wk::launch_lattice_gather(d_log_probs, batch, T, vocab, w, st);
+    wk::dispatch_R(w.ls, [&](auto r) {
+      hipLaunchKernelGGL(wk::ctc_loss_recur_kernel<decltype(r)::value>, dim3((unsigned)(2 * batch)), dim3(64), 0, st, T, w);
+    });
     if (d_grad_or_null) {
       const bool vec = vocab % 4 == 0 && !(((uintptr_t)d_log_probs | (uintptr_t)d_grad_or_null) & 15);
       const int mean = reduction == WK_CTC_REDUCTION_MEAN;
@@ -465,8 +340,7 @@ wk_status wk_ctc_loss(const float* d_log_probs, int64_t batch, int32_t T, int32_
                            d_grad_or_null, T, vocab, batch, mean, grad_scale, w);
     }
     hipLaunchKernelGGL(wk::ctc_loss_finish_kernel, dim3(1), dim3(256), 0, st, batch, reduction, zero_infinity, w, d_nll, d_loss);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? WK_OK : hip_fail(e, "wk_ctc_loss launch");
+    return wk::ctc_launched("wk_ctc_loss");
   });
 }
 

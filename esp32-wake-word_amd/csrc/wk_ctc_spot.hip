@@ -18,7 +18,8 @@
 //
 // Two launches on the caller's stream (one without `normalize`), no host
 // synchronisation, no atomics:
-//   rowmax   a wave per frame t < Tb: 16-byte loads, a DPP reduction, g[b][t];
+//   rowmax   a wave per frame t < Tb: 16-byte loads (RowSplit,
+//            wk_ctc_lattice_dev.h), a DPP reduction (wave_max), g[b][t];
 //   recur    one wave per (utterance, keyword), the keywords of one utterance
 //            adjacent in the grid so that they share its rows in L2.  Lane j
 //            holds state j and its carried start frame; the values of states
@@ -37,38 +38,21 @@
 #include <math.h>
 
 #include "wakeword.h"
-#include "wk_common.h"
-#include "wk_kernels.h"
+#include "wk_ctc_lattice_dev.h"
 
 namespace wk {
 namespace {
 
 constexpr int kSpotMaxLen = 32;              // L = 63 states: one lane each
-constexpr int kSpotMaxVocab = 65536;
-constexpr int64_t kSpotMaxFrames = (int64_t)1 << 28;   // batch * T
 constexpr int64_t kSpotMaxPairs = (int64_t)1 << 24;    // batch * n_keywords
 constexpr int kSpotGroup = 16;               // rows in flight per wave
 constexpr int kSpotTrace = 64;               // frames per stored trace row (and per g load): one per lane
 
 int64_t ctc_spot_bytes(int64_t batch, int32_t T) {      // g [batch][T]
-  return (4 * batch * T + 255) & ~(int64_t)255;
+  return round_up_256(4 * batch * T);
 }
-
-__device__ __forceinline__ float neg_inf() { return -__builtin_inff(); }
 
 // ---- row maximum --------------------------------------------------------------------
-template <int CTRL> __device__ __forceinline__ float max_dpp(float v) { return fmaxf(v, dpp<CTRL>(v)); }
-
-// Maximum over the 64 lanes, in every lane.  All lanes active.
-__device__ __forceinline__ float wave_max(float v) {
-  v = max_dpp<0xB1>(v);    // quad_perm [1,0,3,2]
-  v = max_dpp<0x4E>(v);    // quad_perm [2,3,0,1]
-  v = max_dpp<0x141>(v);   // row_half_mirror
-  v = max_dpp<0x140>(v);   // row_mirror
-  const auto rl = [](float x, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), l)); };
-  return fmaxf(fmaxf(rl(v, 0), rl(v, 16)), fmaxf(rl(v, 32), rl(v, 48)));
-}
-
 __global__ __launch_bounds__(256) void ctc_spot_rowmax_kernel(const float* __restrict__ lp, const int32_t* __restrict__ in_len,
                                                               int64_t rows, int T, int V, float* __restrict__ g) {
   const int lane = threadIdx.x & 63;
@@ -78,32 +62,19 @@ __global__ __launch_bounds__(256) void ctc_spot_rowmax_kernel(const float* __res
   const int Tb = in_len ? min(max(in_len[b], 0), T) : T;
   if (t >= Tb) return;
   const float* p = lp + row * V;
-  // The row as head (up to the first 16-byte boundary), quads, tail.
-  const int head = min((int)((4 - (((uintptr_t)p >> 2) & 3)) & 3), V);
-  const int nq = (V - head) >> 2;
-  const int tail0 = head + 4 * nq;
-  float m = lane < head ? p[lane] : neg_inf();
-  const float4* q4 = reinterpret_cast<const float4*>(p + head);
+  const RowSplit r = row_split(p, V);
+  float m = lane < r.head ? p[lane] : neg_inf();
 #pragma unroll 4
-  for (int q = lane; q < nq; q += 64) {
-    const float4 v = q4[q];
+  for (int q = lane; q < r.nq; q += 64) {
+    const float4 v = r.q4[q];
     m = fmaxf(m, fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w)));
   }
-  if (tail0 + lane < V) m = fmaxf(m, p[tail0 + lane]);
+  if (r.tail0 + lane < V) m = fmaxf(m, p[r.tail0 + lane]);
   m = wave_max(m);
   if (lane == 0) g[row] = m;
 }
 
 // ---- recurrence ---------------------------------------------------------------------
-// The previous lane's value (wave_shr:1); lane 0 gets `first`.
-__device__ __forceinline__ int prev_lane(int first, int v) { return __builtin_amdgcn_update_dpp(first, v, 0x138, 0xF, 0xF, false); }
-__device__ __forceinline__ float prev_lane(float first, float v) {
-  return __int_as_float(prev_lane(__float_as_int(first), __float_as_int(v)));
-}
-__device__ __forceinline__ float read_lane(float v, int lane) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
-}
-
 template <bool NORM, bool TRACE>
 __global__ __launch_bounds__(64) void ctc_spot_recur_kernel(const float* __restrict__ lp, const int32_t* __restrict__ in_len,
                                                             const int32_t* __restrict__ kw, int kw_stride,
@@ -221,14 +192,13 @@ __global__ __launch_bounds__(64) void ctc_spot_recur_kernel(const float* __restr
 }  // namespace
 }  // namespace wk
 
-using wk::hip_fail;
 using wk::invalid;
 
 extern "C" {
 
 int64_t wk_ctc_spot_workspace_bytes(int64_t batch, int32_t T, int32_t n_keywords, int32_t max_keyword_len) {
   if (batch <= 0 || T <= 0 || n_keywords <= 0 || max_keyword_len < 1 || max_keyword_len > wk::kSpotMaxLen ||
-      batch > wk::kSpotMaxFrames || batch * T > wk::kSpotMaxFrames || batch * n_keywords > wk::kSpotMaxPairs)
+      batch > wk::kCtcMaxFrames || batch * T > wk::kCtcMaxFrames || batch * n_keywords > wk::kSpotMaxPairs)
     return 0;
   return wk::ctc_spot_bytes(batch, T);
 }
@@ -243,8 +213,8 @@ wk_status wk_ctc_spot(const float* d_log_probs, int64_t batch, int32_t T, int32_
     return invalid("wk_ctc_spot: batch, T, vocab and n_keywords must be positive");
   if (max_keyword_len < 1 || max_keyword_len > wk::kSpotMaxLen) return invalid("wk_ctc_spot: max_keyword_len must be in [1, 32]");
   if (keyword_stride < max_keyword_len) return invalid("wk_ctc_spot: keyword_stride < max_keyword_len");
-  if (vocab > wk::kSpotMaxVocab) return invalid("wk_ctc_spot: vocab > 65536");
-  if (batch > wk::kSpotMaxFrames || batch * T > wk::kSpotMaxFrames) return invalid("wk_ctc_spot: batch * T > 2^28");
+  if (vocab > wk::kCtcMaxVocab) return invalid("wk_ctc_spot: vocab > 65536");
+  if (batch > wk::kCtcMaxFrames || batch * T > wk::kCtcMaxFrames) return invalid("wk_ctc_spot: batch * T > 2^28");
   if (batch * n_keywords > wk::kSpotMaxPairs) return invalid("wk_ctc_spot: batch * n_keywords > 2^24");
   if ((uintptr_t)d_workspace & 15) return invalid("wk_ctc_spot: d_workspace must be 16-byte aligned");
   if (device < 0) return invalid("wk_ctc_spot: device < 0");
@@ -267,8 +237,7 @@ wk_status wk_ctc_spot(const float* d_log_probs, int64_t batch, int32_t T, int32_
       if (d_frame_scores_or_null) launch(wk::ctc_spot_recur_kernel<false, true>);
       else launch(wk::ctc_spot_recur_kernel<false, false>);
     }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? WK_OK : hip_fail(e, "wk_ctc_spot launch");
+    return wk::ctc_launched("wk_ctc_spot");
   });
 }
 

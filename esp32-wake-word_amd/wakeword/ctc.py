@@ -181,6 +181,69 @@ def pad_targets(targets, target_lengths):
     return out
 
 
+def _check_log_probs(log_probs) -> None:
+    import torch
+    if not (torch.is_tensor(log_probs) and log_probs.is_cuda and log_probs.dtype == torch.float32 and log_probs.dim() == 3):
+        raise ValueError("log_probs must be a 3-D float32 tensor on the HIP device")
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _stream_ptr(device):
+    """The current stream of `device` as the C ABI takes it."""
+    import torch
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def _workspace(nbytes: int, device, unsupported: str):
+    """A wk_*_workspace_bytes result as a device buffer (the caching
+    allocator's: no device malloc per call); 0 bytes means the shape is beyond
+    the kernels' limits: WakewordError(unsupported)."""
+    import torch
+    if nbytes <= 0:
+        raise _lib.WakewordError(unsupported)
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def _lengths(x, device):
+    """Lengths as a tensor or sequence -> a flat contiguous int32 tensor on `device`."""
+    import torch
+    return torch.as_tensor(x).reshape(-1).to(device=device, dtype=torch.int32).contiguous()
+
+
+def _label_args(lp, targets, input_lengths, target_lengths):
+    """ctc_loss's label arguments for (B, T, V) log-probs lp -> (labels, in_len,
+    lab_len, max_label_len), the tensors wk_ctc_loss and wk_ctc_align read, on
+    lp's device."""
+    B = lp.shape[0]
+    labels = pad_targets(targets, target_lengths).to(lp.device).contiguous()
+    in_len, lab_len = _lengths(input_lengths, lp.device), _lengths(target_lengths, lp.device)
+    if labels.shape[0] != B or in_len.numel() != B or lab_len.numel() != B:
+        raise ValueError(f"batch of {B}: targets {tuple(labels.shape)}, {in_len.numel()} input and {lab_len.numel()} target lengths")
+    max_label_len = labels.shape[1]
+    if max_label_len > MAX_LABEL_LEN:      # padding wider than the kernels' limit: the longest label decides (a host sync)
+        max_label_len = int(lab_len.max())
+    return labels, in_len, lab_len, max_label_len
+
+
+def _wk_ctc_loss(lp, labels, in_len, lab_len, max_label_len, reduction: str, zero_infinity, want_grad: bool, unsupported: str):
+    """One wk_ctc_loss call on the current stream -> (nll (B,), loss (1,), the
+    gradient at the logits or None)."""
+    import torch
+    B, T, V = lp.shape
+    L = lib()
+    ws = _workspace(L.wk_ctc_loss_workspace_bytes(B, T, max_label_len), lp.device, unsupported)
+    nll = torch.empty(B, dtype=torch.float32, device=lp.device)
+    loss = torch.empty(1, dtype=torch.float32, device=lp.device)
+    grad = torch.empty_like(lp) if want_grad else None
+    check(L.wk_ctc_loss(_ptr(lp), B, T, V, _ptr(labels), labels.shape[1], _ptr(in_len), _ptr(lab_len), max_label_len,
+                        _lib.WK_CTC_REDUCTION[reduction], int(zero_infinity), 1.0, _ptr(ws), _ptr(nll), _ptr(loss), _ptr(grad),
+                        lp.device.index, _stream_ptr(lp.device)), "wk_ctc_loss")
+    return nll, loss, grad
+
+
 _loss_fn = None
 
 
@@ -192,26 +255,14 @@ def _ctc_loss_fn():
         return _loss_fn
     import torch
 
-    def ptr(t):
-        return C.c_void_p(t.data_ptr())
-
     class CTCLossFn(torch.autograd.Function):
         @staticmethod
         def forward(ctx, lp, labels, in_len, lab_len, max_label_len, reduction, zero_infinity):
-            B, T, V = lp.shape
-            L = lib()
-            nbytes = L.wk_ctc_loss_workspace_bytes(B, T, max_label_len)
-            if nbytes <= 0:
-                raise _lib.WakewordError(f"wk_ctc_loss: unsupported shape (B={B}, T={T}, max label length {max_label_len} "
-                                         f"> {MAX_LABEL_LEN}?)")
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=lp.device)
-            nll = torch.empty(B, dtype=torch.float32, device=lp.device)
-            loss = torch.empty(1, dtype=torch.float32, device=lp.device)
-            grad = torch.empty_like(lp) if ctx.needs_input_grad[0] else None
-            check(L.wk_ctc_loss(ptr(lp), B, T, V, ptr(labels), labels.shape[1], ptr(in_len), ptr(lab_len), max_label_len,
-                                _lib.WK_CTC_REDUCTION[reduction], int(zero_infinity), 1.0, ptr(ws), ptr(nll), ptr(loss),
-                                ptr(grad) if grad is not None else None, lp.device.index,
-                                C.c_void_p(torch.cuda.current_stream(lp.device).cuda_stream)), "wk_ctc_loss")
+            B, T, _ = lp.shape
+            nll, loss, grad = _wk_ctc_loss(lp, labels, in_len, lab_len, max_label_len, reduction, zero_infinity,
+                                           ctx.needs_input_grad[0],
+                                           f"wk_ctc_loss: unsupported shape (B={B}, T={T}, max label length {max_label_len} "
+                                           f"> {MAX_LABEL_LEN}?)")
             ctx.per_utterance = reduction == "none"
             ctx.save_for_backward(grad)
             return nll if reduction == "none" else loss.reshape(())
@@ -238,21 +289,11 @@ def ctc_loss(log_probs, targets, input_lengths, target_lengths, reduction: str =
     this call (torch's native convention, exact through log_softmax's backward)
     and backward() only scales it by grad_output (per utterance for
     reduction="none")."""
-    import torch
     if reduction not in _lib.WK_CTC_REDUCTION:
         raise ValueError(f"reduction must be 'none', 'sum' or 'mean', got {reduction!r}")
-    if not (torch.is_tensor(log_probs) and log_probs.is_cuda and log_probs.dtype == torch.float32 and log_probs.dim() == 3):
-        raise ValueError("log_probs must be a 3-D float32 tensor on the HIP device")
+    _check_log_probs(log_probs)
     lp = (log_probs if batch_first else log_probs.transpose(0, 1)).contiguous()
-    B = lp.shape[0]
-    labels = pad_targets(targets, target_lengths).to(lp.device).contiguous()
-    in_len = torch.as_tensor(input_lengths).reshape(-1).to(device=lp.device, dtype=torch.int32).contiguous()
-    lab_len = torch.as_tensor(target_lengths).reshape(-1).to(device=lp.device, dtype=torch.int32).contiguous()
-    if labels.shape[0] != B or in_len.numel() != B or lab_len.numel() != B:
-        raise ValueError(f"batch of {B}: targets {tuple(labels.shape)}, {in_len.numel()} input and {lab_len.numel()} target lengths")
-    max_label_len = labels.shape[1]
-    if max_label_len > MAX_LABEL_LEN:      # padding wider than the kernels' limit: the longest label decides (a host sync)
-        max_label_len = int(lab_len.max())
+    labels, in_len, lab_len, max_label_len = _label_args(lp, targets, input_lengths, target_lengths)
     return _ctc_loss_fn().apply(lp, labels, in_len, lab_len, max_label_len, reduction, bool(zero_infinity))
 
 
@@ -290,18 +331,8 @@ def _align_args(log_probs, targets, input_lengths, target_lengths, batch_first: 
     """ctc_align's arguments as ctc_loss takes them -> (lp (B, T, V), labels,
     in_len, lab_len, max_label_len), the tensors wk_ctc_align reads, on
     log_probs' device."""
-    import torch
     lp = (log_probs if batch_first else log_probs.transpose(0, 1)).detach().contiguous()
-    B = lp.shape[0]
-    labels = pad_targets(targets, target_lengths).to(lp.device).contiguous()
-    in_len = torch.as_tensor(input_lengths).reshape(-1).to(device=lp.device, dtype=torch.int32).contiguous()
-    lab_len = torch.as_tensor(target_lengths).reshape(-1).to(device=lp.device, dtype=torch.int32).contiguous()
-    if labels.shape[0] != B or in_len.numel() != B or lab_len.numel() != B:
-        raise ValueError(f"batch of {B}: targets {tuple(labels.shape)}, {in_len.numel()} input and {lab_len.numel()} target lengths")
-    max_label_len = labels.shape[1]
-    if max_label_len > MAX_LABEL_LEN:      # padding wider than the kernels' limit: the longest label decides (a host sync)
-        max_label_len = int(lab_len.max())
-    return lp, labels, in_len, lab_len, max_label_len
+    return (lp, *_label_args(lp, targets, input_lengths, target_lengths))
 
 
 def ctc_align(log_probs, targets, input_lengths, target_lengths, batch_first: bool = False) -> Alignment:
@@ -314,28 +345,20 @@ def ctc_align(log_probs, targets, input_lengths, target_lengths, batch_first: bo
     defined bit for bit by the recurrence and tie rule in include/wakeword.h.
     span_seconds converts the spans to time."""
     import torch
-    if not (torch.is_tensor(log_probs) and log_probs.is_cuda and log_probs.dtype == torch.float32 and log_probs.dim() == 3):
-        raise ValueError("log_probs must be a 3-D float32 tensor on the HIP device")
+    _check_log_probs(log_probs)
     lp, labels, in_len, lab_len, max_label_len = _align_args(log_probs, targets, input_lengths, target_lengths, batch_first)
     B, T, V = lp.shape
-    L = lib()
-    nbytes = L.wk_ctc_align_workspace_bytes(B, T, max_label_len)
-    if nbytes <= 0:
-        raise _lib.WakewordError(f"wk_ctc_align: unsupported shape (B={B}, T={T}, max label length {max_label_len} "
-                                 f"> {MAX_LABEL_LEN}?)")
-    dev = lp.device
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)      # (the caching allocator's: no device malloc per call)
+    L, dev, ptr = lib(), lp.device, _ptr
+    ws = _workspace(L.wk_ctc_align_workspace_bytes(B, T, max_label_len), dev,
+                    f"wk_ctc_align: unsupported shape (B={B}, T={T}, max label length {max_label_len} > {MAX_LABEL_LEN}?)")
     states = torch.empty((B, T), dtype=torch.int32, device=dev)
     tokens = torch.empty((B, T), dtype=torch.int32, device=dev)
     frame_lp = torch.empty((B, T), dtype=torch.float32, device=dev)
     spans = torch.empty((B, max_label_len, 2), dtype=torch.int32, device=dev)
     scores = torch.empty((B,), dtype=torch.float32, device=dev)
-
-    def ptr(t):
-        return C.c_void_p(t.data_ptr())
     check(L.wk_ctc_align(ptr(lp), B, T, V, ptr(labels), labels.shape[1], ptr(in_len), ptr(lab_len), max_label_len, ptr(ws),
-                         ptr(states), ptr(tokens), ptr(frame_lp), ptr(spans), ptr(scores), dev.index,
-                         C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "wk_ctc_align")
+                         ptr(states), ptr(tokens), ptr(frame_lp), ptr(spans), ptr(scores), dev.index, _stream_ptr(dev)),
+          "wk_ctc_align")
     return Alignment(states, tokens, frame_lp, spans, scores)
 
 
@@ -373,7 +396,6 @@ def _beam_args(log_probs, input_lengths, beam, top_k, n_best, max_len, batch_fir
     """ctc_beam_search's arguments -> (lp (B, T, V), in_len or None, max_len),
     what wk_ctc_beam reads, on log_probs' device; ValueError for what the
     kernels do not take."""
-    import torch
     for name, v, lo, hi in (("beam", beam, 1, MAX_BEAM), ("top_k", top_k, 1, MAX_TOP_K), ("n_best", n_best, 1, beam)):
         if not isinstance(v, int) or isinstance(v, bool) or not lo <= v <= hi:
             raise ValueError(f"{name} must be an integer in [{lo}, {hi}], got {v!r}")
@@ -387,7 +409,7 @@ def _beam_args(log_probs, input_lengths, beam, top_k, n_best, max_len, batch_fir
         raise ValueError(f"max_len must be a positive integer, got {max_len!r}")
     in_len = None
     if input_lengths is not None:
-        in_len = torch.as_tensor(input_lengths).reshape(-1).to(device=lp.device, dtype=torch.int32).contiguous()
+        in_len = _lengths(input_lengths, lp.device)
         if in_len.numel() != B:
             raise ValueError(f"batch of {B}: {in_len.numel()} input lengths")
     return lp, in_len, max_len
@@ -404,25 +426,18 @@ def ctc_beam_search(log_probs, input_lengths=None, beam: int = 16, top_k: int = 
     max_len, the width of the token rows, defaults to T.  Runs on the current
     stream, no host sync."""
     import torch
-    if not (torch.is_tensor(log_probs) and log_probs.is_cuda and log_probs.dtype == torch.float32 and log_probs.dim() == 3):
-        raise ValueError("log_probs must be a 3-D float32 tensor on the HIP device")
+    _check_log_probs(log_probs)
     lp, in_len, max_len = _beam_args(log_probs, input_lengths, beam, top_k, n_best, max_len, batch_first)
     B, T, V = lp.shape
-    L = lib()
-    nbytes = L.wk_ctc_beam_workspace_bytes(B, T, beam, top_k)
-    if nbytes <= 0:
-        raise _lib.WakewordError(f"wk_ctc_beam: unsupported shape (B={B}, T={T}, beam={beam}, top_k={top_k})")
-    dev = lp.device
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)      # (the caching allocator's: no device malloc per call)
+    L, dev, ptr = lib(), lp.device, _ptr
+    ws = _workspace(L.wk_ctc_beam_workspace_bytes(B, T, beam, top_k), dev,
+                    f"wk_ctc_beam: unsupported shape (B={B}, T={T}, beam={beam}, top_k={top_k})")
     tokens = torch.empty((B, n_best, max_len), dtype=torch.int32, device=dev)
     lengths = torch.empty((B, n_best), dtype=torch.int32, device=dev)
     scores = torch.empty((B, n_best), dtype=torch.float32, device=dev)
     cand = torch.empty((B, T, top_k), dtype=torch.int32, device=dev) if return_candidates else None
-
-    def ptr(t):
-        return C.c_void_p(t.data_ptr()) if t is not None else None
     check(L.wk_ctc_beam(ptr(lp), B, T, V, ptr(in_len), beam, top_k, n_best, max_len, ptr(ws), ptr(tokens), ptr(lengths),
-                        ptr(scores), ptr(cand), dev.index, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "wk_ctc_beam")
+                        ptr(scores), ptr(cand), dev.index, _stream_ptr(dev)), "wk_ctc_beam")
     return BeamResult(tokens, lengths, scores, cand)
 
 
@@ -502,7 +517,7 @@ def _spot_args(log_probs, keywords, keyword_lengths, input_lengths, batch_first:
     K = kw.shape[0]
     if keyword_lengths is None:
         keyword_lengths = [kw.shape[1]] * K
-    kl = torch.as_tensor(keyword_lengths).reshape(-1).to(device=lp.device, dtype=torch.int32).contiguous()
+    kl = _lengths(keyword_lengths, lp.device)
     if kl.numel() != K:
         raise ValueError(f"{K} keywords: {kl.numel()} keyword lengths")
     max_len = kw.shape[1]
@@ -512,7 +527,7 @@ def _spot_args(log_probs, keywords, keyword_lengths, input_lengths, batch_first:
             raise ValueError(f"a keyword of {max_len} labels: at most {MAX_KEYWORD_LEN}")
     in_len = None
     if input_lengths is not None:
-        in_len = torch.as_tensor(input_lengths).reshape(-1).to(device=lp.device, dtype=torch.int32).contiguous()
+        in_len = _lengths(input_lengths, lp.device)
         if in_len.numel() != B:
             raise ValueError(f"batch of {B}: {in_len.numel()} input lengths")
     return lp, kw, kl, in_len, max_len
@@ -535,26 +550,18 @@ def ctc_spot(log_probs, keywords, keyword_lengths=None, input_lengths=None, norm
     recurrence and tie rule in include/wakeword.h.  span_seconds converts the
     spans to time."""
     import torch
-    if not (torch.is_tensor(log_probs) and log_probs.is_cuda and log_probs.dtype == torch.float32 and log_probs.dim() == 3):
-        raise ValueError("log_probs must be a 3-D float32 tensor on the HIP device")
+    _check_log_probs(log_probs)
     lp, kw, kl, in_len, max_len = _spot_args(log_probs, keywords, keyword_lengths, input_lengths, batch_first)
     B, T, V = lp.shape
     K = kw.shape[0]
-    L = lib()
-    nbytes = L.wk_ctc_spot_workspace_bytes(B, T, K, max_len)
-    if nbytes <= 0:
-        raise _lib.WakewordError(f"wk_ctc_spot: unsupported shape (B={B}, T={T}, {K} keywords, max keyword length {max_len})")
-    dev = lp.device
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)      # (the caching allocator's: no device malloc per call)
+    L, dev, ptr = lib(), lp.device, _ptr
+    ws = _workspace(L.wk_ctc_spot_workspace_bytes(B, T, K, max_len), dev,
+                    f"wk_ctc_spot: unsupported shape (B={B}, T={T}, {K} keywords, max keyword length {max_len})")
     scores = torch.empty((B, K), dtype=torch.float32, device=dev)
     spans = torch.empty((B, K, 2), dtype=torch.int32, device=dev)
     trace = torch.empty((B, K, T), dtype=torch.float32, device=dev) if frame_scores else None
-
-    def ptr(t):
-        return C.c_void_p(t.data_ptr()) if t is not None else None
     check(L.wk_ctc_spot(ptr(lp), B, T, V, ptr(in_len), ptr(kw), kw.shape[1], ptr(kl), K, max_len, 1 if normalize else 0, ptr(ws),
-                        ptr(scores), ptr(spans), ptr(trace), dev.index, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
-          "wk_ctc_spot")
+                        ptr(scores), ptr(spans), ptr(trace), dev.index, _stream_ptr(dev)), "wk_ctc_spot")
     return Spot(scores, spans, trace)
 
 
@@ -664,7 +671,7 @@ def _cer_args(hyp, hyp_lengths, ref, ref_lengths, collapse: bool):
     h = h.contiguous()
     hl = None
     if hyp_lengths is not None:
-        hl = torch.as_tensor(hyp_lengths).reshape(-1).to(device=h.device, dtype=torch.int32).contiguous()
+        hl = _lengths(hyp_lengths, h.device)
         if hl.numel() != B * H:
             raise ValueError(f"{B} x {H} hypotheses: {hl.numel()} hypothesis lengths")
     elif not collapse:
@@ -675,7 +682,7 @@ def _cer_args(hyp, hyp_lengths, ref, ref_lengths, collapse: bool):
     if r.shape[1] == 0:
         r = torch.zeros((r.shape[0], 1), dtype=torch.int32, device=r.device)
     r = r.to(device=h.device, dtype=torch.int32).contiguous()
-    rl = torch.as_tensor(ref_lengths).reshape(-1).to(device=h.device, dtype=torch.int32).contiguous()
+    rl = _lengths(ref_lengths, h.device)
     if r.shape[0] != B or rl.numel() != B:
         raise ValueError(f"batch of {B}: ref {tuple(r.shape)}, {rl.numel()} reference lengths")
     max_ref_len = r.shape[1]
@@ -705,21 +712,14 @@ def edit_distance(hyp, hyp_lengths, ref, ref_lengths, collapse: bool = False) ->
     squeeze = hyp.dim() == 2
     h, hl, r, rl, max_ref_len = _cer_args(hyp, hyp_lengths, ref, ref_lengths, collapse)
     B, H, stride = h.shape
-    L = lib()
-    nbytes = L.wk_ctc_cer_workspace_bytes(B, H, stride, max_ref_len)
-    if nbytes <= 0:
-        raise _lib.WakewordError(f"wk_ctc_cer: unsupported shape (B={B}, n_hyp={H}, N={stride}, max reference length {max_ref_len})")
-    dev = h.device
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)      # (the caching allocator's: no device malloc per call)
+    L, dev, ptr = lib(), h.device, _ptr
+    ws = _workspace(L.wk_ctc_cer_workspace_bytes(B, H, stride, max_ref_len), dev,
+                    f"wk_ctc_cer: unsupported shape (B={B}, n_hyp={H}, N={stride}, max reference length {max_ref_len})")
     stats = torch.empty((B, H, 4), dtype=torch.int32, device=dev)
     best = torch.empty((B,), dtype=torch.int32, device=dev)
     totals = torch.empty((2, 8), dtype=torch.int64, device=dev)
-
-    def ptr(t):
-        return C.c_void_p(t.data_ptr()) if t is not None else None
     check(L.wk_ctc_cer(ptr(h), ptr(hl), B, H, stride, ptr(r), r.shape[1], ptr(rl), max_ref_len, 1 if collapse else 0, ptr(ws),
-                       ptr(stats), ptr(best), ptr(totals), dev.index, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
-          "wk_ctc_cer")
+                       ptr(stats), ptr(best), ptr(totals), dev.index, _stream_ptr(dev)), "wk_ctc_cer")
     cols = [stats[:, 0, k] if squeeze else stats[:, :, k] for k in range(4)]
     return EditStats(cols[0], cols[1], cols[2], cols[3], best, totals)
 
@@ -764,7 +764,7 @@ class CTCModel:
             pass
 
     def _stream(self, torch):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return _stream_ptr(self.device)
 
     def features(self, audio, n_samples: int = MAX_AUDIO_SAMPLES):
         """(B, L) float waveform -> (B, T, 80) on device, T = 1 + n_samples // 160."""
@@ -997,34 +997,13 @@ class CTCModel:
     def _loss_and_flat_grad(self, feats, targets, input_lengths, target_lengths, reduction: str = "mean",
                             zero_infinity: bool = False, dropout=None, seed: int = 0, offset: int = 0):
         """loss_and_grad with the gradient as backward() returns it: one flat tensor."""
-        import torch
         if reduction not in _lib.WK_CTC_REDUCTION:
             raise ValueError(f"reduction must be 'none', 'sum' or 'mean', got {reduction!r}")
         lp = self.forward_train(feats, dropout, seed, offset)
-        B, T, V = lp.shape
-        labels = pad_targets(targets, target_lengths).to(lp.device).contiguous()
-        in_len = torch.as_tensor(input_lengths).reshape(-1).to(device=lp.device, dtype=torch.int32).contiguous()
-        lab_len = torch.as_tensor(target_lengths).reshape(-1).to(device=lp.device, dtype=torch.int32).contiguous()
-        if labels.shape[0] != B or in_len.numel() != B or lab_len.numel() != B:
-            raise ValueError(f"batch of {B}: targets {tuple(labels.shape)}, {in_len.numel()} input and {lab_len.numel()} "
-                             f"target lengths")
-        max_label_len = labels.shape[1]
-        if max_label_len > MAX_LABEL_LEN:
-            max_label_len = int(lab_len.max())
-        L = lib()
-        nbytes = L.wk_ctc_loss_workspace_bytes(B, T, max_label_len)
-        if nbytes <= 0:
-            raise _lib.WakewordError(f"wk_ctc_loss: unsupported shape (B={B}, T={T}, max label length {max_label_len})")
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=lp.device)
-        nll = torch.empty(B, dtype=torch.float32, device=lp.device)
-        loss = torch.empty(1, dtype=torch.float32, device=lp.device)
-        grad = torch.empty_like(lp)
-
-        def ptr(t):
-            return C.c_void_p(t.data_ptr())
-        check(L.wk_ctc_loss(ptr(lp), B, T, V, ptr(labels), labels.shape[1], ptr(in_len), ptr(lab_len), max_label_len,
-                            _lib.WK_CTC_REDUCTION[reduction], int(zero_infinity), 1.0, ptr(ws), ptr(nll), ptr(loss),
-                            ptr(grad), self.device, self._stream(torch)), "wk_ctc_loss")
+        B, T, _ = lp.shape
+        labels, in_len, lab_len, max_label_len = _label_args(lp, targets, input_lengths, target_lengths)
+        nll, loss, grad = _wk_ctc_loss(lp, labels, in_len, lab_len, max_label_len, reduction, zero_infinity, True,
+                                       f"wk_ctc_loss: unsupported shape (B={B}, T={T}, max label length {max_label_len})")
         flat, norm = self.backward(grad, return_norm=True)
         return (nll if reduction == "none" else loss.reshape(())), flat, norm
 

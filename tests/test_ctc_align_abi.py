@@ -69,6 +69,14 @@ def test_workspace_bytes(L):
         assert f(*bad) == 0
 
 
+def test_workspace_bytes_pinned(L):
+    """The sizes themselves, at each register layout's last and first label
+    length (31 | 32, 127, 255) and at T = 801."""
+    f = L.wk_ctc_align_workspace_bytes
+    assert f(8, 801, 31) == 3314944 and f(8, 801, 32) == 4955392
+    assert f(3, 17, 127) == 99840 and f(257, 5, 255) == 3259904
+
+
 def test_span_seconds():
     import wakeword
     spans = np.array([[[0, 3], [3, 50]], [[-1, -1], [-1, -1]]], dtype=np.int32)

@@ -81,6 +81,13 @@ def test_workspace_bytes(L):
         assert f(*bad) == 0
 
 
+def test_workspace_bytes_pinned(L):
+    """The sizes themselves: (batch, T, beam, top_k), T = 801 among them."""
+    f = L.wk_ctc_beam_workspace_bytes
+    assert f(8, 801, 16, 16) == 1666304 and f(1, 1, 1, 1) == 256
+    assert f(3, 17, 64, 32) == 39424 and f(257, 5, 5, 3) == 89600
+
+
 def test_wrapper_rejects_bad_arguments():
     import wakeword
     from wakeword import ctc

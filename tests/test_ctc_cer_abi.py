@@ -89,6 +89,13 @@ def test_workspace_bytes(L):
     assert f(8, 16, 8191, 1024) <= f(8, 16, 1, 1024) + 4 * 8 * 16 * 8191 + 256      # at most the collapsed hypotheses
 
 
+def test_workspace_bytes_pinned(L):
+    """The sizes themselves: (batch, n_hyp, hyp_stride, max_ref_len), 801-frame hypotheses among them."""
+    f = L.wk_ctc_cer_workspace_bytes
+    assert f(8, 1, 801, 40) == 256 and f(1, 1, 1, 1) == 256
+    assert f(3, 64, 17, 1024) == 1536 and f(257, 4, 5, 9) == 8448
+
+
 def test_wrapper_rejects_bad_arguments():
     import wakeword
     from wakeword import ctc

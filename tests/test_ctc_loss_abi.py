@@ -67,6 +67,15 @@ def test_workspace_bytes(L):
         assert f(*bad) == 0
 
 
+def test_workspace_bytes_pinned(L):
+    """The sizes themselves, at each register layout's last and first label
+    length (31 | 32, 127, 255) and at T = 801: the layout is the kernels'
+    contract with their callers' buffers, so a change of it shows here."""
+    f = L.wk_ctc_loss_workspace_bytes
+    assert f(8, 801, 31) == 4923648 and f(8, 801, 32) == 9844992
+    assert f(3, 17, 127) == 160000 and f(257, 5, 255) == 8424704
+
+
 def test_pad_targets_concatenated_equals_padded():
     import wakeword
     c = R.case("S32-T70-V33-B3", "random")       # lengths 32, 31, 0

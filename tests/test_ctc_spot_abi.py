@@ -75,6 +75,13 @@ def test_workspace_bytes(L):
     assert f(8, 801, 1, 4) < L.wk_ctc_align_workspace_bytes(8, 801, 4)
 
 
+def test_workspace_bytes_pinned(L):
+    """The sizes themselves: (batch, T, n_keywords, max_keyword_len), T = 801 among them."""
+    f = L.wk_ctc_spot_workspace_bytes
+    assert f(8, 801, 3, 5) == 25856 and f(1, 1, 1, 1) == 256
+    assert f(3, 17, 2, 32) == 256 and f(257, 5, 7, 9) == 5376
+
+
 def test_keyword_tokens():
     import wakeword
     c2i = {"a": 1, "b": 2, "c": 3, "小": 4}
