@@ -69,6 +69,9 @@ struct wk_ctc {
   DevBuf<float2> tr_part;      // [tr_slots] per-wave log-mel statistics (ctc_logmel_fft2_kernel<true>)
   DevBuf<float2> tr_zs;
   size_t tr_rows, tr_batch, tr_slots;
+  int64_t tr_last_batch;   // geometry and path of the last wk_ctc_transcribe (wk_ctc_transcribe_stats); T 0: none yet
+  int32_t tr_last_T;
+  bool tr_last_fused;
   int64_t last_batch;   // geometry of the last wk_ctc_forward (wk_ctc_frame_argmax)
   int32_t last_T;
   // training (fp32 handles; wk_ctc_forward_train / wk_ctc_backward): W_hh as the backward's GEMM operand
@@ -492,6 +495,7 @@ wk_status wk_ctc_transcribe(wk_ctc* c, const float* d_audio, int64_t batch, int3
     hipStream_t st = (hipStream_t)stream;
     hipError_t e;
     const int64_t slots = ctc_logmel_layout(c->n_cu, rows, T).slots;
+    c->tr_last_T = 0;   // (set once every stage is enqueued)
     if ((size_t)rows > c->tr_rows || (size_t)batch > c->tr_batch || (size_t)slots > c->tr_slots) {   // grows, then reused
       if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(e, "sync");
       c->tr_rows = c->tr_batch = c->tr_slots = 0;
@@ -508,7 +512,31 @@ wk_status wk_ctc_transcribe(wk_ctc* c, const float* d_audio, int64_t batch, int3
     wk_status s = ctc_features(c, d_audio, batch, n_valid, n_samples, stride, c->tr_feats, stream,
                                fused ? c->tr_part : nullptr, fused ? c->tr_zs : nullptr);
     if (s != WK_OK) return s;
-    return ctc_forward(c, c->tr_feats, batch, T, nullptr, d_tokens, d_lengths, stream, fused ? c->tr_zs : nullptr);
+    s = ctc_forward(c, c->tr_feats, batch, T, nullptr, d_tokens, d_lengths, stream, fused ? c->tr_zs : nullptr);
+    if (s != WK_OK) return s;
+    c->tr_last_batch = batch;
+    c->tr_last_T = T;
+    c->tr_last_fused = fused;
+    return WK_OK;
+  });
+}
+
+wk_status wk_ctc_transcribe_stats(wk_ctc* c, int64_t batch, int32_t T, float* d_raw, float* d_zs, void* stream) {
+  if (!c || batch < 0 || T < 1) return invalid("wk_ctc_transcribe_stats: bad arguments");
+  if (c->tr_last_T == 0) return invalid("wk_ctc_transcribe_stats: no wk_ctc_transcribe on this handle yet");
+  if (!c->tr_last_fused || batch != c->tr_last_batch || T != c->tr_last_T)
+    return invalid(("wk_ctc_transcribe_stats: the handle's last wk_ctc_transcribe had batch " + std::to_string(c->tr_last_batch) +
+                    ", T " + std::to_string(c->tr_last_T) +
+                    (c->tr_last_fused ? " (fused)" : c->f16 ? ", not fused (T < 6)" : ", not fused (fp32 handle)") +
+                    "; asked for batch " + std::to_string(batch) + ", T " + std::to_string(T))
+                       .c_str());
+  return on_device(c->cfg.device, [&]() -> wk_status {
+    hipStream_t st = (hipStream_t)stream;
+    const size_t rows = (size_t)batch * (size_t)T;
+    hipError_t e = hipSuccess;
+    if (d_raw) e = hipMemcpyAsync(d_raw, c->tr_feats.get(), sizeof(float) * rows * kMels, hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess && d_zs) e = hipMemcpyAsync(d_zs, c->tr_zs.get(), sizeof(float2) * (size_t)batch, hipMemcpyDeviceToDevice, st);
+    return e == hipSuccess ? WK_OK : hip_fail(e, "wk_ctc_transcribe_stats");
   });
 }
 

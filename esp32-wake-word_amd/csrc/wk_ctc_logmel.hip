@@ -95,6 +95,17 @@ __device__ __forceinline__ void dft20(f2 (&x)[20]) {
 //            1/4 of the separation rides in the mel weights (exact);
 //   mel:     straight-line per-lane windows (weights in registers), one
 //            8-byte read per pair and tap feeding two FMAs, then ln(+1e-8).
+// The separation is exact only in exact arithmetic: in fp32 each frame of a
+// pair receives the FFT's rounding asymmetry of the other, <= ~1e-13 of the
+// partner's power per bin.  Against a frame with any signal at a supported
+// level (down to 1e-3 of full scale) that is below its own rounding; against
+// an all-zero frame (zero padding, digital silence) next to int16-scaled
+// audio it is ~1e-4 per bin, far above the 1e-8 floor.  So a frame whose 400
+// loaded samples are all exactly zero is given power exactly 0: its lane
+// group votes on the raw samples, and the row's mel sums are zeroed ahead of
+// the logarithm (wave-uniform branches, taken only by passes that hold such
+// a frame).  Every mel value of the frame is then ln(1e-8f) bit for bit and
+// its STATS terms are exactly 0.  A quiet but non-zero frame keeps the leak.
 // One 12-wave workgroup per CU (3 waves per SIMD), the tables once per CU.
 // LDS pitches (see the per-access notes) keep the stage-1 writes, stage-2
 // reads and pair-power writes free of bank conflicts.
@@ -252,6 +263,25 @@ __global__ __launch_bounds__(kF2Waves * 64, 1) void ctc_logmel_fft2_kernel(const
       }
       asm volatile("" ::: "memory");   // ahead of the next pass's loads
     }
+    // All-zero frames (see the header): the lane groups vote on the raw
+    // samples (sign bit aside: -0 is zero) before the next pass's overwrite
+    // them -- first on the 20 centre samples 200 + q alone, and only a wave
+    // with a frame whose centre is all zero looks at the rest.  Bit f of zmask
+    // (wave-uniform): row f of the pass is all zero.
+    constexpr unsigned long long kGrp = 0xFFFFFull;   // a lane group's 20 lanes
+    auto zero_groups = [&](unsigned long long nz) {   // bit 2 g: group g has no lane set in nz
+      return ((nz & kGrp) == 0 ? 1u : 0u) | ((nz >> 20 & kGrp) == 0 ? 4u : 0u) | ((nz >> 40 & kGrp) == 0 ? 16u : 0u);
+    };
+    unsigned zmask = 0;
+    if (zero_groups(__ballot((__float_as_uint(ra[10]) << 1) != 0)) | zero_groups(__ballot((__float_as_uint(rb[10]) << 1) != 0))) {
+      unsigned ba = 0, bb = 0;
+#pragma unroll
+      for (int n1 = 0; n1 < 20; n1 += 2) {
+        ba |= __float_as_uint(ra[n1]) | __float_as_uint(ra[n1 + 1]);
+        bb |= __float_as_uint(rb[n1]) | __float_as_uint(rb[n1 + 1]);
+      }
+      zmask = zero_groups(__ballot((ba << 1) != 0)) | zero_groups(__ballot((bb << 1) != 0)) << 1;
+    }
     load_pair(ps + 1 < p_end, ra, rb);
     dft20(v);
     // A rows: lane (g, q) writes A[g][q][0..19]; pitch 25 float2 = 50 dwords:
@@ -377,7 +407,12 @@ __global__ __launch_bounds__(kF2Waves * 64, 1) void ctc_logmel_fft2_kernel(const
       const int64_t r0 = ps * kRowsPerPass;
       const int64_t nr = rows - r0 < kRowsPerPass ? rows - r0 : kRowsPerPass;
       const __amdgpu_buffer_rsrc_t fr = make_rsrc(feats + r0 * kMels, (uint32_t)(nr > 0 ? nr : 0) * kMels * 4);
-      const float av[6] = {a0.x, a0.y, a1.x, a1.y, a2.x, a2.y};
+      float av[6] = {a0.x, a0.y, a1.x, a1.y, a2.x, a2.y};
+      if (zmask) {   // (wave-uniform, rare) an all-zero row has power 0, not the separation's rounding of its partner's
+#pragma unroll
+        for (int f = 0; f < 6; ++f)
+          if (zmask >> f & 1) av[f] = cv[f] = 0.0f;
+      }
       const bool half0 = lane < 2 * (kMels - 64) && (lane & 1) == 0;
       const int o2 = half0 ? 4 * (64 + (lane >> 1)) : 0x40000000;
       float la[6], lc[6];

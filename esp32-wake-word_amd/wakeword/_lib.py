@@ -39,7 +39,8 @@ EXPORTS = ("wk_create", "wk_destroy", "wk_mfcc", "wk_cnn", "wk_forward", "wk_syn
            "wk_ctc_set_weights", "wk_ctc_adam_step", "wk_ctc_optim_state", "wk_ctc_set_optim_state",
            "wk_ctc_forward_train_dropout", "wk_ctc_dropout_masks", "wk_augment_batch",
            "wk_ctc_align_workspace_bytes", "wk_ctc_align", "wk_ctc_beam_workspace_bytes", "wk_ctc_beam",
-           "wk_ctc_spot_workspace_bytes", "wk_ctc_spot", "wk_ctc_cer_workspace_bytes", "wk_ctc_cer")
+           "wk_ctc_spot_workspace_bytes", "wk_ctc_spot", "wk_ctc_cer_workspace_bytes", "wk_ctc_cer",
+           "wk_ctc_transcribe_stats")
 WK_CTC_REDUCTION = {"none": 0, "sum": 1, "mean": 2}
 WK_NUM_INT8_WEIGHTS = 3 * 13 * 32 + 3 * 32 * 64 + 3 * 64 * 128 + 128 * 64 + 64
 WK_QUANT_TENSORS = 7
@@ -213,6 +214,9 @@ def _declare(L):
         L.wk_ctc_cer_workspace_bytes.restype = i64
         L.wk_ctc_cer.argtypes = [vp, vp, i64, i32, i32, vp, i32, vp, i32, i32, vp, vp, vp, vp, i32, vp]
         L.wk_ctc_cer.restype = i32
+    if hasattr(L, "wk_ctc_transcribe_stats"):
+        L.wk_ctc_transcribe_stats.argtypes = [vp, i64, i32, vp, vp, vp]
+        L.wk_ctc_transcribe_stats.restype = i32
     for name in ("wk_create", "wk_destroy", "wk_mfcc", "wk_cnn", "wk_forward", "wk_synth_clips", "wk_normalize",
                  "wk_stream_create", "wk_stream_destroy", "wk_stream_reset", "wk_stream_push", "wk_ctc_create",
                  "wk_ctc_destroy", "wk_ctc_features", "wk_ctc_forward", "wk_wav_read", "wk_wav_load_batch",

@@ -820,6 +820,18 @@ class CTCModel:
               "wk_ctc_frame_argmax")
         return out
 
+    def transcribe_stats(self, batch: int, T: int, return_raw: bool = False):
+        """The z-score statistics of the last decode_audio on this model, when it
+        took the fused path (fp16, T >= 6; else WakewordError): (batch, 2)
+        float32 {mean, 1/std} per utterance on device, and with return_raw
+        also the (batch, T, 80) un-normalised log-mel rows they are of."""
+        import torch
+        zs = torch.empty((batch, 2), dtype=torch.float32, device=f"cuda:{self.device}")
+        raw = torch.empty((batch, T, 80), dtype=torch.float32, device=zs.device) if return_raw else None
+        check(lib().wk_ctc_transcribe_stats(self._h, batch, T, _ptr(raw), _ptr(zs), self._stream(torch)),
+              "wk_ctc_transcribe_stats")
+        return (zs, raw) if return_raw else zs
+
     def forward(self, feats, return_log_probs: bool = False):
         """(B, T, 80) -> token id lists (greedy CTC, decode_predictions'
         output form), and (B, T, V) log-probs if asked."""

@@ -312,6 +312,15 @@ wk_status wk_ctc_stage_times(wk_ctc* c, double* ms_sum /* [WK_CTC_N_STAGES] */, 
  * must be that call's (else WK_ERR_INVALID_ARG); stream-ordered after it. */
 wk_status wk_ctc_frame_argmax(wk_ctc* c, int64_t batch, int32_t T, int32_t* d_pred, void* stream);
 
+/* What the z-score of the handle's last wk_ctc_transcribe was computed from,
+ * when that call took the fused path (fp16 handle, T >= 6): the un-normalised
+ * log-mel rows ln(mel + 1e-8) to d_raw_or_null [batch][T][80] and each
+ * utterance's {mean, 1/std} ({0, 1} for std 0) to d_zs_or_null [batch][2],
+ * copied stream-ordered after it.  batch and T must be that call's and the
+ * call fused, else WK_ERR_INVALID_ARG (the message names the last call). */
+wk_status wk_ctc_transcribe_stats(wk_ctc* c, int64_t batch, int32_t T, float* d_raw_or_null, float* d_zs_or_null,
+                                  void* stream);
+
 /* ---- CTC head: parameter gradients (the backward half of ctc.py:380-407) -----
  * fp32 handles only (precision 0; a precision-1 handle: WK_ERR_UNSUPPORTED
  * before any device work).  The function differentiated is the one the

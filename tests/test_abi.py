@@ -67,6 +67,7 @@ def test_bad_arguments_rejected_without_gpu(L):
     assert L.wk_ctc_features(None, None, 1, 48000, 48000, 48000, None, None) == 1
     assert L.wk_ctc_forward(None, None, 1, 301, None, None, None, None) == 1
     assert L.wk_ctc_transcribe(None, None, 1, 48000, 48000, 48000, None, None, None) == 1
+    assert L.wk_ctc_transcribe_stats(None, 1, 301, None, None, None) == 1
 
 
 def test_analyze_mfcc_range_output(L, capfd):

@@ -437,12 +437,8 @@ def test_ctc_transcribe_constant_inputs(ctc, kind, n):
     two-call path (features() z-scored by its own double-precision kernel,
     ctc.py:101-104): digital silence (std 0: left un-normalised by both), a DC
     offset (non-silent, the log-mel far from constant) and a batch alternating
-    the two.  The mixed batch uses T = 50: the log-mel kernel transforms two
-    consecutive frames per complex FFT, and with an odd T the last frame of
-    one utterance shares its FFT with the first of the next, which puts
-    ~eps^2 of the DC frame's power (above the 1e-8 floor) into the silent
-    frame -- a constant utterance is then only constant to rounding, and its
-    z-score (noise / noise, as torch's own for silence) is ill-conditioned."""
+    the two (T = 50 here; the odd T = 51, where a silent frame shares its FFT
+    with a DC one, is in tests/test_gpu_ctc_logmel.py)."""
     import wakeword
     m, _ = ctc
     g = wakeword.CTCModel(CO.flat_weights(m), V, precision="fp16")
