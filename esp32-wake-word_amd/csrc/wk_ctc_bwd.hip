@@ -29,7 +29,7 @@
 // inputs give equal bits.  No workgroup waits on another.
 #include <math.h>
 
-#include "wk_ctc_dev.h"
+#include "wk_ctc_handle.h"
 
 using namespace wk;
 
@@ -385,7 +385,7 @@ struct Operand {
   int64_t s_outer, s_k;   // element strides: along m (A) or n (B), and along k
 };
 
-// The partials workspace, as launch_ctc_backward was given it.
+// The partials workspace: the training workspace's, at its capacity.
 struct Part {
   float* p;
   size_t floats;
@@ -453,66 +453,52 @@ size_t ctc_bwd_part_floats(int V, int64_t rows) {
 }
 
 void launch_ctc_backward(const CtcBwd& a, hipStream_t st) {
+  const CtcTrainWs& s = a.ws;
+  const CtcWeights& w = a.w;
   const int64_t rows = a.B * a.T;
   const int V = a.V, H = kH;
-  float* g = a.grads;
-  // blob offsets (wk_ctc_create's order)
-  const size_t o_encw = 0, o_encb = (size_t)H * kMels, o_lng = o_encb + H, o_lnb = o_lng + H;
-  size_t o_wih[2][2], o_whh[2][2], o_bih[2][2], o_bhh[2][2];
-  size_t o = o_lnb + H;
-  for (int l = 0; l < 2; ++l)
-    for (int d = 0; d < 2; ++d) {
-      const size_t din = l == 0 ? H : 2 * H;
-      o_wih[l][d] = o;
-      o += 3 * H * din;
-      o_whh[l][d] = o;
-      o += 3 * (size_t)H * H;
-      o_bih[l][d] = o;
-      o += 3 * H;
-      o_bhh[l][d] = o;
-      o += 3 * H;
-    }
-  const size_t o_outw = o, o_outb = o + (size_t)V * 2 * H;
-  const Part part{a.part, a.part_floats};
+  const CtcBlob blob = ctc_blob(V);
+  auto g = [&](int seg) { return a.grads + blob.off[seg]; };   // a segment's gradient
+  const Part part{s.part, ctc_bwd_part_floats(V, (int64_t)s.rows)};
 
   // output layer: db = sum g, dW = g^T y1, dy1 = g W
-  colsum(st, a.dlogits, rows, V, V, g + o_outb);
-  gemm(st, V, 2 * H, rows, {a.dlogits, 1, V}, {a.y[1], 1, 2 * H}, g + o_outw, 2 * H, part);
-  gemm(st, (int)rows, 2 * H, V, {a.dlogits, V, 1}, {a.out_w, 1, 2 * H}, a.dya, 2 * H, part);
+  colsum(st, a.dlogits, rows, V, V, g(kSegOutB));
+  gemm(st, V, 2 * H, rows, {a.dlogits, 1, V}, {s.y[1], 1, 2 * H}, g(kSegOutW), 2 * H, part);
+  gemm(st, (int)rows, 2 * H, V, {a.dlogits, V, 1}, {w.out_w, 1, 2 * H}, s.dya, 2 * H, part);
   for (int l = 1; l >= 0; --l) {
     const int din = l == 0 ? H : 2 * H;
-    const float* x = l == 0 ? a.x0 : a.x1;
-    const float* dy = l == 1 ? a.dya : a.dyb;
-    float* dx = l == 1 ? a.dyb : a.dya;
-    hipLaunchKernelGGL(ctc_bwd_shift_kernel, dim3(grid_for(rows * (2 * H / 4), a.n_cu)), dim3(256), 0, st, a.y[l], rows, a.T,
-                       a.hprev);
+    const float* x = l == 0 ? s.x0 : s.drop.on[1] ? s.y0d : s.y[0];
+    const float* dy = l == 1 ? s.dya : s.dyb;
+    float* dx = l == 1 ? s.dyb : s.dya;
+    hipLaunchKernelGGL(ctc_bwd_shift_kernel, dim3(grid_for(rows * (2 * H / 4), a.n_cu)), dim3(256), 0, st, s.y[l].get(), rows, a.T,
+                       s.hprev.get());
     for (int d = 0; d < 2; ++d)   // gh = h_prev W_hh^T
-      gemm(st, (int)rows, 3 * H, H, {a.hprev + d * H, 2 * H, 1}, {a.whh[l] + (size_t)d * 3 * H * H, H, 1}, a.gh + d * 3 * H,
+      gemm(st, (int)rows, 3 * H, H, {s.hprev + d * H, 2 * H, 1}, {w.whh[l] + (size_t)d * 3 * H * H, H, 1}, s.gh + d * 3 * H,
            6 * H, part);
-    hipLaunchKernelGGL(ctc_bwd_gates_kernel, dim3(grid_for(rows * 2 * H, a.n_cu)), dim3(256), 0, st, a.gi[l], a.gh, a.hprev,
-                       a.bih[l], a.bhh[l], rows, a.coef);
+    hipLaunchKernelGGL(ctc_bwd_gates_kernel, dim3(grid_for(rows * 2 * H, a.n_cu)), dim3(256), 0, st, s.gi[l].get(), s.gh.get(),
+                       s.hprev.get(), w.bih[l].get(), w.bhh[l].get(), rows, s.coef.get());
     hipLaunchKernelGGL(ctc_gru_bptt_kernel, dim3((unsigned)((a.B + kBpBatch - 1) / kBpBatch), 2), dim3(kBpThreads), 0, st,
-                       a.coef, dy, a.whht_pk[l], a.B, a.T, a.da_i, a.da_h);
+                       s.coef.get(), dy, w.whht_pk[l].get(), a.B, a.T, s.da_i.get(), s.da_h.get());
     for (int d = 0; d < 2; ++d) {
-      gemm(st, 3 * H, din, rows, {a.da_i + d * 3 * H, 1, 6 * H}, {x, 1, din}, g + o_wih[l][d], din, part);
-      gemm(st, 3 * H, H, rows, {a.da_h + d * 3 * H, 1, 6 * H}, {a.hprev + d * H, 1, 2 * H}, g + o_whh[l][d], H, part);
-      colsum(st, a.da_i + d * 3 * H, rows, 6 * H, 3 * H, g + o_bih[l][d]);
-      colsum(st, a.da_h + d * 3 * H, rows, 6 * H, 3 * H, g + o_bhh[l][d]);
+      gemm(st, 3 * H, din, rows, {s.da_i + d * 3 * H, 1, 6 * H}, {x, 1, din}, g(ctc_gru_seg(l, d, kGruWih)), din, part);
+      gemm(st, 3 * H, H, rows, {s.da_h + d * 3 * H, 1, 6 * H}, {s.hprev + d * H, 1, 2 * H}, g(ctc_gru_seg(l, d, kGruWhh)), H, part);
+      colsum(st, s.da_i + d * 3 * H, rows, 6 * H, 3 * H, g(ctc_gru_seg(l, d, kGruBih)));
+      colsum(st, s.da_h + d * 3 * H, rows, 6 * H, 3 * H, g(ctc_gru_seg(l, d, kGruBhh)));
     }
     // dx = da_i [rows][fwd 384 | rev 384] W_ih [fwd rows; rev rows]: both directions' shares in one product
-    gemm(st, (int)rows, din, 6 * H, {a.da_i, 6 * H, 1}, {a.wih[l], 1, din}, dx, din, part);
+    gemm(st, (int)rows, din, 6 * H, {s.da_i, 6 * H, 1}, {w.wih[l], 1, din}, dx, din, part);
     // the layer's input went through dropout site l: dx <- s m dx (site 0: x0 > 0 below already implies m; s is still due)
-    if (a.drop.on[l]) launch_ctc_dropout_bwd(a.drop, l, dx, rows, a.n_cu, st);
+    if (s.drop.on[l]) launch_ctc_dropout_bwd(s.drop, l, dx, rows, a.n_cu, st);
   }
-  // encoder (dx0 = a.dya [rows][128])
-  gemm(st, (int)rows, H, kMels, {a.feats, kMels, 1}, {a.enc_w, kMels, 1}, a.pre, H, part);
-  hipLaunchKernelGGL(ctc_bwd_layernorm_kernel, dim3(grid_for(rows * 64, a.n_cu)), dim3(256), 0, st, a.pre, a.enc_b, a.ln_g, a.x0,
-                     a.dya, rows, a.t0, a.t1);
-  colsum(st, a.t1, rows, H, H, g + o_lng);
-  colsum(st, a.t0, rows, H, H, g + o_lnb);
-  colsum(st, a.pre, rows, H, H, g + o_encb);
-  gemm(st, H, kMels, rows, {a.pre, 1, H}, {a.feats, 1, kMels}, g + o_encw, kMels, part);
-  if (a.norm) hipLaunchKernelGGL(ctc_bwd_norm_kernel, dim3(1), dim3(1024), 0, st, g, (int64_t)(o_outb + V), a.norm);
+  // encoder (dx0 = s.dya [rows][128])
+  gemm(st, (int)rows, H, kMels, {s.feats, kMels, 1}, {w.enc_w, kMels, 1}, s.pre, H, part);
+  hipLaunchKernelGGL(ctc_bwd_layernorm_kernel, dim3(grid_for(rows * 64, a.n_cu)), dim3(256), 0, st, s.pre.get(), w.enc_b.get(),
+                     w.ln_g.get(), s.x0.get(), s.dya.get(), rows, s.t0.get(), s.t1.get());
+  colsum(st, s.t1, rows, H, H, g(kSegLnG));
+  colsum(st, s.t0, rows, H, H, g(kSegLnB));
+  colsum(st, s.pre, rows, H, H, g(kSegEncB));
+  gemm(st, H, kMels, rows, {s.pre, 1, H}, {s.feats, 1, kMels}, g(kSegEncW), kMels, part);
+  if (a.norm) hipLaunchKernelGGL(ctc_bwd_norm_kernel, dim3(1), dim3(1024), 0, st, a.grads, blob.off[kCtcSegs], a.norm);
 }
 
 void launch_ctc_bwd_norm(const float* g, int64_t n, float* out, hipStream_t st) {

@@ -1,6 +1,7 @@
 // wk_ctc_dev.h -- what the units of the GRU-CTC head share (internal): the
 // model's fixed sizes, the fp16 fragment vectors, one wave reduction, and the
-// launchers wk_ctc.hip (the C ABI, no kernels) calls into the per-stage units:
+// launchers the two ABI units (no kernels: wk_ctc.hip, inference; wk_ctc_train.hip,
+// the fp32-handle entry points; their handle: wk_ctc_handle.h) call into the per-stage units:
 //
 //   wk_ctc_logmel.hip  X1   log-mel front end + z-score, its host tables
 //   wk_ctc_dense.hip   X2a  encoder (fp32 / fp16), the block GEMM, fp16 <-> fp32 copy
@@ -144,28 +145,26 @@ void launch_ctc_dropout_mask(const CtcDrop& d, int site, uint8_t* mask, int64_t 
 // ---- wk_ctc_bwd.hip ---------------------------------------------------------
 // W_hh [2 dir][384][128] fp32 -> ctc_gru_bptt_kernel's fragments of W_hh^T ([2][8 unit tiles][96 k-steps][64 lanes]).
 std::vector<float> ctc_pack_whht(const float* whh);
-// Floats of the split-K partials workspace (CtcBwd::part) for vocabulary V and rows = B T.
+// Floats of the split-K partials workspace (CtcTrainWs::part) for vocabulary V and rows = B T.
 size_t ctc_bwd_part_floats(int V, int64_t rows);
-// One backward pass (fp32), all device pointers.  Saved by the training
-// forward: feats [rows][80], x0 [rows][128], gi[l] [rows][768] (no bias), y[l]
-// [rows][256].  Weights as uploaded by wk_ctc_create (wih[l] [768][din], whh[l]
-// [2][384][128], bih / bhh [768]).  Scratch: hprev, dya, dyb [rows][256]; gh,
-// da_i, da_h [rows][768]; coef [rows][1280]; pre, t0, t1 [rows][128]; part.
-// grads: the parameter blob's layout; norm (or null): its 2-norm.
-// Dropout (drop.on[s]; all off when zero-initialised): x0 is then the dropped
-// encoder output (masked in place by the forward), x1 is layer 1's input -- the
-// dropped copy of y[0], or y[0] itself with site 1 off -- and y[0] stays the
-// undropped output, layer 0's h_prev.
+// One backward pass (fp32) at geometry B x T <= ws.rows: what the training
+// forward saved in ws and its scratch there (sizes: CtcTrainWs::table), the
+// weights as wk_ctc_create uploaded them, and the caller's device pointers:
+// dlogits [B][T][V]; grads: the parameter blob's layout (ctc_blob); norm (or
+// null): its 2-norm.  Dropout (ws.drop.on[s]): ws.x0 is then the dropped
+// encoder output (masked in place by the forward), layer 1's input is the
+// dropped copy ws.y0d, or ws.y[0] itself with site 1 off, and ws.y[0] stays the
+// undropped output, layer 0's h_prev.  The split-K partials ws.part hold
+// ctc_bwd_part_floats(V, ws.rows): the workspace's capacity, not this call's rows.
+struct CtcTrainWs;   // (wk_ctc_handle.h)
+struct CtcWeights;
 struct CtcBwd {
   int64_t B;
   int T, V, n_cu;
-  const float *feats, *x0, *x1, *gi[2], *y[2];
-  CtcDrop drop;
-  const float *enc_w, *enc_b, *ln_g, *wih[2], *whh[2], *whht_pk[2], *bih[2], *bhh[2], *out_w;
-  float *hprev, *dya, *dyb, *gh, *da_i, *da_h, *coef, *pre, *t0, *t1, *part;
-  size_t part_floats;   // of part: ctc_bwd_part_floats(V, rows), or more
   const float* dlogits;
   float *grads, *norm;
+  const CtcTrainWs& ws;
+  const CtcWeights& w;
 };
 void launch_ctc_backward(const CtcBwd& a, hipStream_t st);
 // out[0] = the 2-norm of g [n], accumulated in double in a fixed order (ctc_bwd_norm_kernel, as launch_ctc_backward runs it).
@@ -177,6 +176,26 @@ void launch_ctc_bwd_norm(const float* g, int64_t n, float* out, hipStream_t st);
 // b_ih, b_hh}, 2 output).  Every off and every len but the last (out_b [V]) is
 // a multiple of 4 floats, and every p is 16-byte aligned.  Passed by value.
 constexpr int kCtcSegs = 22;
+// The blob's layout, stated once for C++ (Python's ctc_state_dict_spec is the independent statement the tests compare
+// with): off[k] is segment k's first float, off[kCtcSegs] the total; segment k holds off[k + 1] - off[k] floats.
+enum { kSegEncW, kSegEncB, kSegLnG, kSegLnB, kSegGru, kSegOutW = kCtcSegs - 2, kSegOutB };
+enum { kGruWih, kGruWhh, kGruBih, kGruBhh };
+constexpr int ctc_gru_seg(int l, int d, int which) { return kSegGru + 4 * (2 * l + d) + which; }
+struct CtcBlob {
+  int64_t off[kCtcSegs + 1];
+};
+inline CtcBlob ctc_blob(int64_t V, int64_t H = kH) {
+  CtcBlob b;
+  int k = 0;
+  int64_t o = 0;
+  auto seg = [&](int64_t len) { b.off[k++] = o, o += len; };
+  seg(H * kMels), seg(H), seg(H), seg(H);   // encoder W, b; LayerNorm gamma, beta
+  for (int l = 0; l < 2; ++l)               // per layer and direction: W_ih, W_hh, b_ih, b_hh
+    for (int d = 0; d < 2; ++d) seg(3 * H * (l == 0 ? H : 2 * H)), seg(3 * H * H), seg(3 * H), seg(3 * H);
+  seg(V * 2 * H), seg(V);
+  b.off[k] = o;
+  return b;
+}
 struct CtcSeg {
   int64_t off, len;
   float* p;

@@ -5,7 +5,8 @@
 // has the lane moves and the log-space sums those recurrences are written in,
 // the register-row layout of the label lattice with its gather and prep steps
 // (loss and align), the split of a V-wide row into aligned 16-byte loads (beam
-// and spot), and the host-side limits and tail the five entry points share.
+// and spot), and the host-side limits the five entry points share (their
+// launch-error tail, ctc_launched, is in wk_kernels.h with the handle units').
 // Each kernel's own layout constants and its tie rule stay in its unit, as
 // wk_ctc_dev.h prescribes; wave_max is beside wave_sum in wk_common.h.
 #pragma once
@@ -23,12 +24,6 @@ constexpr int64_t kCtcMaxFrames = (int64_t)1 << 28;    // batch * T: one block (
 constexpr int kCtcLatticeMaxLabels = 255;              // L = 511 states: 8 registers per lane
 
 inline int64_t round_up_256(int64_t bytes) { return (bytes + 255) & ~(int64_t)255; }
-
-// The end of an entry point's on_device body: a launch error of any of its kernels as "<fn> launch: ...".
-inline wk_status ctc_launched(const char* fn) {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? WK_OK : hip_fail(e, (std::string(fn) + " launch").c_str());
-}
 
 // ---- lanes --------------------------------------------------------------------------
 __device__ __forceinline__ float neg_inf() { return -__builtin_inff(); }

@@ -28,6 +28,12 @@ wk_status on_device(int dev, F body) {
   return s;
 }
 
+// The end of a wk_ctc_* entry point's on_device body: a launch error of any of its kernels as "<fn> launch: ...".
+inline wk_status ctc_launched(const char* fn) {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? WK_OK : hip_fail(e, (std::string(fn) + " launch").c_str());
+}
+
 // Front-end (wk_frontend.hip).  mode_b: torchaudio+CMVN -> [B][13][63];
 // otherwise esp_mfcc -> [B][n_frames][13].
 hipError_t launch_frontend(bool mode_b, bool i16, const void* audio, int64_t batch, int win_len,

@@ -27,7 +27,7 @@ SOURCES = ["wk_frontend.hip", "wk_fused.hip", "wk_fused_xdl.hip", "wk_misc.hip",
            "wk_ctc_dense.hip", "wk_ctc_gru.hip", "wk_ctc_out.hip", "wk_wav.cpp", "wk_int8.hip", "wk_esp_mfcc.hip",
            "wk_scan.hip", "wk_train.hip", "wk_quant.hip", "wk_ctc_loss.hip", "wk_ctc_bwd.hip", "wk_ctc_optim.hip", "wk_stream.hip",
            "wk_compat.hip", "wk_ctc_dropout.hip", "wk_augment.hip", "wk_ctc_align.hip", "wk_ctc_beam.hip",
-           "wk_ctc_spot.hip", "wk_ctc_cer.hip"]
+           "wk_ctc_spot.hip", "wk_ctc_cer.hip", "wk_ctc_train.hip"]
 LIBS = ["-Wl,-rpath,/opt/rocm/lib"]   # HIP runtime only: every GEMM is a hand-written kernel (no rocBLAS)
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("WK_OFFLOAD_ARCH", "gfx950")
